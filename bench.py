@@ -5,8 +5,20 @@ inner step, DIST/simulators.py:190-196), W = communication_graph("circle",
 "stochastic", 8192) seeded 2028 (the reference's own construction, ring
 kernel).  Inputs are synthetic fp32 (randn), resident in HBM before timing.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed
+steps (HIP events around every launch price the ring kernel in `roofline`),
+the optional output dump, the line.  `--full` adds every other measurement:
+the copy-kernel calibration of `roofline`, the CPU baselines and the
+secondaries below (each with its own --no-* switch).
+
+`--dump-outputs DIR` writes what the last timed step computed (the mixed agent
+rows a caller of ShardedRing.step() reads back) as float32 DIR/<name>.npy:
+the whole matrix when it fits the dump budget, else a fixed seeded sample of
+whole rows and of columns over all rows.  Inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 
 Without a launcher, `--gpus N > 1` starts the N ranks itself (child
 processes, before any GPU call) and relays rank 0's line; a run whose joined
@@ -19,9 +31,9 @@ rank; each round exchanges the two boundary rows with the neighbouring ranks
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the
 ring mix) from HIP events around every launch in the timed region;
-`cpu_baseline` times the reference-structured torch-CPU round
+with --full, `cpu_baseline` times the reference-structured torch-CPU round
 (oracle/ref_cpu.py) on this host on a bounded sample (N=1 only).
-Secondaries (N=1, skipped with --no-primal-dual): FedADMM round (config 4),
+Secondaries (--full, N=1, skipped with --no-primal-dual): FedADMM round (config 4),
 FedLCon eps = 5 fused pass, random 4-regular mix on the parameter-major bank,
 the Erdos-Renyi mix on the matrix cores (split3) and bit-exact, and a whole
 config-5 round (ER draw + device Neighbors + fused MLP local step + exact mix).
@@ -78,10 +90,19 @@ def parse():
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_ring_8192x1M.json"))
     ap.add_argument("--no-primal-dual", action="store_true", help="skip the secondary measurements (primal/dual round, FedLCon eps=5, dense ER mix)")
     ap.add_argument("--pd-steps", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the copy-kernel calibration, the CPU baselines and "
+                         "the secondary measurements (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as float32 DIR/<name>.npy "
+                         "(a fixed seeded sample when the matrix exceeds the dump budget)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only bring the ranks up: every rank joins the process group and rank 0 prints the "
                          "world each rank saw (the launcher's own test; no kernels, no GPU needed under gloo)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_copy = args.no_primal_dual = True
+    return args
 
 
 def _free_port() -> int:
@@ -886,6 +907,45 @@ def config5_round(device, N: int = 1024, reps: int = 10):
     return out
 
 
+DUMP_BUDGET_BYTES = 32 << 20  # the whole dump stays well below 64 MB
+
+
+def dump_outputs(dirname: str, ring, world: int, rank: int) -> dict:
+    """--dump-outputs: the timed path's result after its last step, i.e. this
+    rank's rows of X after ring.step() (ring.x[:, :P], what a caller reads
+    back), as float32 .npy files.  A matrix within DUMP_BUDGET_BYTES is written
+    whole (`x`); a larger one as a fixed sample drawn with seed 2028 from its
+    shape alone: whole rows (`x_rows`: the first, the last and random ones) and
+    columns over all rows (`x_cols`), half the budget each, with the sampled
+    indices beside them (`x_rows_index` / `x_cols_index`, float64).  At world
+    > 1 every rank writes its block with a `.rank<r>` suffix."""
+    os.makedirs(dirname, exist_ok=True)
+    n, P = ring.n_local, ring.P
+    X = ring.x[:n, :P]
+    sfx = f".rank{rank}" if world > 1 else ""
+    arrays = {}
+    if n * P * 4 <= DUMP_BUDGET_BYTES:
+        arrays["x"] = X.cpu().numpy()
+    else:
+        rng = np.random.default_rng(2028)
+        half = DUMP_BUDGET_BYTES // 2
+        n_rows = max(1, min(n, half // (P * 4)))
+        rows = np.unique(np.concatenate([[0], rng.choice(n, n_rows, replace=False)]))[:n_rows]  # sorted, row 0 first
+        if n_rows >= 2:
+            rows[-1] = n - 1
+        n_cols = max(1, min(P, half // (n * 4)))
+        cols = np.sort(rng.choice(P, n_cols, replace=False))
+        arrays["x_rows"] = X[torch.as_tensor(rows, device=X.device)].cpu().numpy()
+        arrays["x_cols"] = X[:, torch.as_tensor(cols, device=X.device)].cpu().numpy()
+        arrays["x_rows_index"] = rows.astype(np.float64)
+        arrays["x_cols_index"] = cols.astype(np.float64)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirname, name + sfx + ".npy"), np.ascontiguousarray(a))
+    return {"dir": dirname, "arrays": {k + sfx: list(a.shape) for k, a in arrays.items()},
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -967,6 +1027,12 @@ def main():
     kern_rows = ring.n_local if world == 1 else ring.n_local - 2
     alg_bytes = 2 * kern_rows * P * 4  # each row read once + written once
     achieved = alg_bytes / (kern_ms / 1e3) / 1e9
+
+    # --dump-outputs: the last timed step's result, before any other leg reuses the buffers
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, ring, world, rank)
+        _log(f"outputs written to {args.dump_outputs}")
 
     # secondary (N = 1): FedLCon's eps = 5 consensus rounds per local update
     # (DIST/simulators.py:190-196) as ONE temporally blocked pass over the same
@@ -1063,6 +1129,8 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic (randn agent parameters, seed 2028)",
+            "full": bool(args.full),
+            "outputs": dumped,
             "config": {
                 "workload": f"ring gossip mix X <- W X, {N} agents x {P} params, W = "
                             f"communication_graph('circle','stochastic',{N}) seed 2028",

@@ -47,6 +47,61 @@ def test_fit_n2_n_noise_cannot_make_a_coefficient_negative(bench):
     assert f2["a_s_per_agent2"] > 0 and f2["b_s_per_agent"] >= 0 and f2["rounds_per_s"] < noisy[256]
 
 
+def test_plain_run_is_headline_only_and_full_restores_the_rest(bench, monkeypatch):
+    """Without --full every leg beside the headline is off; with it each leg
+    follows its own --no-* switch as before."""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu and a.no_copy and a.no_primal_dual
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_cpu or a.no_copy or a.no_primal_dual)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.no_cpu and not a.no_copy and not a.no_primal_dual and a.dump_outputs == "d"
+
+
+def _fake_ring(n, P, ld):
+    import types
+
+    import torch
+    x = torch.arange(n * ld, dtype=torch.float32).reshape(n, ld)
+    return types.SimpleNamespace(n_local=n, P=P, x=x)
+
+
+def test_dump_outputs_small_matrix_is_written_whole(bench, tmp_path):
+    import numpy as np
+    ring = _fake_ring(5, 37, 40)
+    info = bench.dump_outputs(str(tmp_path / "o"), ring, 1, 0)
+    x = np.load(tmp_path / "o" / "x.npy")
+    assert x.dtype == np.float32 and x.shape == (5, 37)
+    assert np.array_equal(x, ring.x[:, :37].numpy())
+    assert info["arrays"] == {"x": [5, 37]} and info["bytes"] == x.nbytes
+
+
+def test_dump_outputs_large_matrix_is_a_fixed_sample(bench, tmp_path, monkeypatch):
+    """Above the budget: whole rows (first and last among them) and columns over
+    all rows, the same indices on every call, within the budget."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    ring = _fake_ring(33, 101, 128)
+    full = ring.x[:, :101].numpy()
+    info = bench.dump_outputs(str(tmp_path / "a"), ring, 1, 0)
+    bench.dump_outputs(str(tmp_path / "b"), ring, 2, 1)
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"x_rows", "x_cols", "x_rows_index", "x_cols_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    rows, cols = got["x_rows_index"].astype(int), got["x_cols_index"].astype(int)
+    assert rows[0] == 0 and rows[-1] == 32 and len(set(rows)) == len(rows) == 2048 // (101 * 4)
+    assert len(set(cols)) == len(cols) == 2048 // (33 * 4)
+    assert np.array_equal(got["x_rows"], full[rows]) and np.array_equal(got["x_cols"], full[:, cols])
+    assert info["bytes"] <= 4096 + 8 * (len(rows) + len(cols))
+    for name, a in got.items():  # the other rank's files: same sample, suffixed names
+        assert np.array_equal(np.load(tmp_path / "b" / f"{name}.rank1.npy"), a)
+
+
 def _bench_env(**extra):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DOL_BENCH_FAIL_RANK")}

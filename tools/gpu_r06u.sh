@@ -7,7 +7,7 @@ timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 tail -1 $O/tests.txt
 timeout -k 10 300 python -u tools/slab_balance_ab.py > $O/ab.jsonl 2> $O/ab.err || { echo "ab failed"; tail -10 $O/ab.err; exit 1; }
 cat $O/ab.jsonl
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
 print('value', d['value'], 'frac', d['roofline']['frac'])

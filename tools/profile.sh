@@ -8,7 +8,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/prof}
-ARGS=${ARGS:---steps 10 --warmup 2 --no-cpu --no-copy}
+ARGS=${ARGS:---full --steps 10 --warmup 2 --no-cpu --no-copy}
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- python3 bench.py $ARGS > "$OUT/trace.log" 2>&1 || { echo "trace pass failed rc=$?"; exit 1; }
 echo "trace ok"
