@@ -50,6 +50,7 @@
 // not bit-exact.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <math.h>
 #include <type_traits>
@@ -1057,8 +1058,18 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
   // dW1's k-chain as two interleaved accumulators summed at the end (VERDICT r02
   // item 4): local step 0.5036-0.5046 vs 0.5074-0.5079 ms with one chain, three
   // alternating pairs on one box (profiles/r03_mlp_dw1_chains.txt) -- the step
-  // is not chain-latency bound; DOL_MLP_DW1_CHAINS=1 restores one chain
-  static const int dw1_chains = [] { const char* e = getenv("DOL_MLP_DW1_CHAINS"); return e ? atoi(e) : 2; }();
+  // is not chain-latency bound.  DOL_MLP_DW1_CHAINS=1 used to restore one chain;
+  // one fma chain rounds differently from two (1 ulp of W1, 1.5e-8 at 784-128-10:
+  // tests/test_mlp_gpu.py::test_step_paths_bit_identical), so it was never the
+  // "same bits" A/B switch it was used as: the setting is refused with a message
+  // and the step runs the two-chain kernels, like every other path.
+  static const int dw1_chains = [] {
+    const char* e = getenv("DOL_MLP_DW1_CHAINS");
+    if (e && atoi(e) != 2)
+      fprintf(stderr, "dol_mlp_step_f32: DOL_MLP_DW1_CHAINS=%s ignored: a one-chain dW1 does not give the default's "
+                      "bits; running two chains\n", e);
+    return 2;
+  }();
   static const int dw1_occ4 = [] { const char* e = getenv("DOL_MLP_DW1_OCC"); return e ? atoi(e) == 4 : 0; }();
   // diagnostics: unused dynamic LDS per dW1 workgroup, to cap its occupancy (DOL_MLP_DW1_LDS bytes, <= 64 KiB)
   static const size_t dw1_lds = [] {
@@ -1148,18 +1159,13 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
       if (nt1) fwd(mlp_fwd_kernel<1, U, TH, AL>, lds);
       else fwd(mlp_fwd_kernel<4, U, TH, AL>, lds);
     }
-    if (dw1_xcd && dw1_occ4 && dw1_chains == 1)
-      hipLaunchKernelGGL((mlp_dw1_occ4_kernel<KS, U, TH, AL, 1, 1>), grid2, block, 0, s, a, ws, n_agents);
-    else if (dw1_xcd && dw1_occ4)
+    (void)dw1_chains;  // always 2 (see above)
+    if (dw1_xcd && dw1_occ4)
       hipLaunchKernelGGL((mlp_dw1_occ4_kernel<KS, U, TH, AL, 2, 1>), grid2, block, 0, s, a, ws, n_agents);
-    else if (dw1_xcd && dw1_chains == 1)
-      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 1, 1>), grid2, block, 0, s, a, ws, n_agents);
     else if (dw1_xcd)
       hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 2, 1>), grid2, block, dw1_lds, s, a, ws, n_agents);
-    else if (dw1_chains == 2)
-      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 2>), grid2, block, 0, s, a, ws, n_agents);
     else
-      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL>), grid2, block, 0, s, a, ws, n_agents);
+      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 2>), grid2, block, 0, s, a, ws, n_agents);
   };
   auto by_upd = [&](auto ks, auto th, auto al) {
     using std::integral_constant;
