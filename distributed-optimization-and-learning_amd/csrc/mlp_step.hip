@@ -25,19 +25,35 @@
 // Phases at 1024 agents (tools/mlp_phase.hip, r02): the forward runs as two
 // lock-stepped waves of 512 workgroups (two per CU by LDS), each ~90 us:
 // staging + F1 56-71 us (4.6 TB/s), F2 + CE 5-6, B2 15-16, HBM idle in the
-// last two.  Tried (r02): agent pieces with the forwards on a side stream and
-// each piece's dW1 on the caller's stream after its forward, so dW1(q)
-// overlaps forward(q + 1): local step 0.496-0.500 ms (2 pieces) / 0.510-0.518
-// (4) vs 0.492-0.493 unsplit, same box (profiles/r02_mlp_split.txt): dropped.
-// Also tried: F1 in 16-wide k chunks (64-B rows) with 4 / 6 stages, 40 / 60 KiB
-// of LDS, so all 1024 workgroups are resident at once: 0.515 / 0.522-0.524 vs
-// 0.505 ms (profiles/r02_mlp_split.txt): dropped.
-// dW1 as the transposed product (operands swapped, so a lane holds 4
-// consecutive W1 columns and W1 / momentum move as 16-B buffer ops, 4 + 4
-// per lane and tile instead of 16 + 16): 0.577-0.579 vs 0.505 ms; each 16-B
-// instruction then touches 32 W1 rows' lines instead of 2 (same profile): dropped.
-// dW1 compiled for >= 5 / 6 waves per SIMD (96 / 80 VGPRs, 20 / 84 B of
-// scratch) instead of 4 (104): 0.534 / 0.761 vs 0.506 ms (same profile).
+// last two.
+//
+// This file holds that one path only.  Launch variants that were measured and
+// dropped (local step at 1024 agents, 784-128-10, B = 32; all gave the
+// default's bits unless noted; none was faster):
+//   r02 (code removed then; profiles/r02_mlp_split.txt): agent pieces on two
+//     streams so dW1(q) overlaps forward(q + 1), 0.496-0.518 vs 0.492-0.493 ms;
+//     F1 in 16-wide k chunks with 4 / 6 stages, 0.515 / 0.522-0.524 vs 0.505;
+//     dW1 as the transposed product with 16-B W1 / momentum accesses (each
+//     touches 32 W1 rows' lines instead of 2), 0.577-0.579 vs 0.505; dW1
+//     compiled for >= 5 / 6 waves per SIMD (scratch), 0.534 / 0.761 vs 0.506.
+//   r02-r04 (code last present at a07f8d3):
+//     F1 pipeline depth 2 / 4 / 5 instead of 3 (profiles/r02_mlp_stages.txt).
+//     The forward as two kernels, F1 and the per-agent tail: 0.487 vs 0.479 ms
+//     (profiles/r03_mlp_split_fwd.txt, r04k_mlp_paths.txt).
+//     The whole step as one kernel with W1 resident in registers (h = 128,
+//     B <= 32): reads W1 once but leaves one workgroup per CU, 0.588 vs 0.56 ms
+//     in tools/mlp_phase.hip (profiles/r03_mlp_fused.txt).
+//     F1 as single-wave (agent, h-tile) workgroups with 3-8 deep rings of 32-
+//     or 64-wide k chunks, and the tail kernel at four waves per SIMD:
+//     0.504-0.557 vs 0.488-0.491 ms (profiles/r04k_mlp_paths.txt,
+//     r05zu_mlp_f1_kw.txt).
+//     dW1 at four waves per SIMD, 0.491 vs 0.472 ms, and with 64 KiB of unused
+//     LDS as an occupancy cap, 0.474-0.477 vs 0.468-0.473 (r04k_mlp_paths.txt).
+//     dW1 tiles in agent-major order: 0.506-0.507 vs 0.478-0.482 ms XCD-grouped
+//     (profiles/r04e_mlp_dw1_xcd_ab.txt; see mlp_dw1_kernel).
+//     dW1 as one k-chain: 0.5074-0.5079 vs 0.5036-0.5046 ms with two, and not
+//     the same bits (1 ulp of W1; profiles/r03_mlp_dw1_chains.txt).
+//
 //   update (every parameter, as dol_prox_admm_sgd_f32):
 //       g' = g [+ (alpha +) rho*(w - theta)];  buf = mom*buf + g' (buf = g' on the
 //       first step);  w = fma(-lr, buf, w)
@@ -167,8 +183,7 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 }
 
 // global -> LDS copy of n floats by the workgroup, N loads in flight per thread
-// (r04): a plain strided loop waits one memory round trip per iteration --
-// the tail of mlp_fwd_kernel PH 2 spent ~16 of them loading H
+// (r04): a plain strided loop waits one memory round trip per iteration
 template <int N, class Src, class Dst>
 __device__ __forceinline__ void lds_fill(int n, Src src, Dst dst) {
   const int t = threadIdx.x;
@@ -197,46 +212,18 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// two arrays in one round trip when each fits one batch
-template <int N1, int N2, class S1, class D1, class S2, class D2>
-__device__ __forceinline__ void lds_fill2(int n1, S1 src1, D1 dst1, int n2, S2 src2, D2 dst2) {
-  if (n1 > N1 * kThreads || n2 > N2 * kThreads) {
-    lds_fill<N1>(n1, src1, dst1);
-    lds_fill<N2>(n2, src2, dst2);
-    return;
-  }
-  const int t = threadIdx.x;
-  float v1[N1], v2[N2];
-#pragma unroll
-  for (int i = 0; i < N1; ++i) v1[i] = src1(i * kThreads + t < n1 ? i * kThreads + t : 0);
-#pragma unroll
-  for (int i = 0; i < N2; ++i) v2[i] = src2(i * kThreads + t < n2 ? i * kThreads + t : 0);
-#pragma unroll
-  for (int i = 0; i < N1; ++i)
-    if (i * kThreads + t < n1) dst1(i * kThreads + t, v1[i]);
-#pragma unroll
-  for (int i = 0; i < N2; ++i)
-    if (i * kThreads + t < n2) dst2(i * kThreads + t, v2[i]);
-}
-
-constexpr int kStages = 3;  // default F1 LDS-DMA pipeline depth (NS - 1 chunks in flight during the MFMAs)
+constexpr int kStages = 3;  // F1 LDS-DMA pipeline depth (kStages - 1 chunks in flight during the MFMAs)
 
 // LDS layout of mlp_fwd_kernel (floats): [ union: F1 staging | Hs, W2s, Zs ] [ b1s, b2s, ls ] [ ys ];
-// the fused kernel (PH 3) keeps them apart: [ staging ] [ Hs, W2s, Zs ] [ ... ]
-__host__ __device__ inline int64_t fwd_staging_floats(int B, int h, int ns) {
-  return int64_t(ns) * (h + 32 * ((B + 31) / 32)) * 32;
-}
-// PH 3: W1 chunks parked in LDS instead of registers (the last KL of NK; 16 KiB each)
-__host__ __device__ constexpr int fused_park_chunks(int nk, int ns) { return nk <= 8 ? 0 : ns <= 4 ? 3 : ns == 5 ? 2 : 0; }
-__host__ __device__ inline int64_t fwd_union_floats(int B, int h, int c, int ns = kStages, bool fused = false,
-                                                    int park = 0) {
-  const int64_t staging = fwd_staging_floats(B, h, ns);
+// the union's size for the host (the kernel computes the same offset in place)
+inline int64_t fwd_union_floats(int B, int h, int c) {
+  const int64_t staging = int64_t(kStages) * (h + 32 * ((B + 31) / 32)) * 32;
   const int64_t post = int64_t(B) * (h + 4) + int64_t(c) * (h + 4) + int64_t(B) * c;
-  return fused ? staging + 4096 * int64_t(park) + post : staging > post ? staging : post;
+  return staging > post ? staging : post;
 }
 
-// Buffer-descriptor memory ops (mlp_fused_dw1, mlp_dw1_kernel): dead lanes
-// point out of range (loads return 0, stores are dropped).
+// Buffer-descriptor memory ops of mlp_dw1_kernel: dead lanes point out of range
+// (loads return 0, stores are dropped).
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 constexpr uint32_t kOOB = 0x80000000u;  // any lane offset >= every buffer's size
 
@@ -249,105 +236,6 @@ __device__ __forceinline__ float bload(rsrc_t r, uint32_t voff, uint32_t soff) {
 __device__ __forceinline__ void bstore_nt(rsrc_t r, uint32_t voff, uint32_t soff, float v) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, static_cast<int>(voff), static_cast<int>(soff), 2);
 }
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// plain (write-back) 16-B stores: each one writes two 16-B pieces of 32 rows, and
-// the nontemporal hint on that pattern made the B1 phase 4x slower (261 vs 66 us
-// per agent, tools/mlp_phase.hip) -- the partial lines must merge in L2
-__device__ __forceinline__ void bstore4(rsrc_t r, uint32_t voff, f4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, static_cast<int>(voff), 0, 0);
-}
-
-// B1 + the W1 update of the fused step (mlp_fwd_kernel PH 3), on the W1 that
-// F1 left in registers.  Per 32-column chunk dt: the dW1^T tile [32 d x 32 h] =
-// X^T dZ1 on MFMA (K = B), with the tile's d rows permuted -- A row i holds
-// column sigma(i) = 16 ((i >> 2) & 1) + 4 (i >> 3) + (i & 3) -- so accumulator
-// r = 4 j + q of lane (li, hh) is the gradient of W1[32 wave + li][32 dt + 16 hh +
-// 4 j + q] = wres[dt][j][q]: exactly where F1 left that weight.  The products
-// and their k order are those of mlp_dw1_kernel with A and B swapped (two
-// chains, even / odd k-steps): bit-identical.  Momentum and X chunks stream
-// through the F1 staging ring (LDS-DMA, NS deep; the first NS - 1 were issued
-// before F2 and landed during F2 .. B2).  W1 / momentum / gradient tiles go out
-// as 16-B buffer stores that are always issued (masked lanes point out of
-// range, absent buffers have size 0), so the per-chunk vmcnt below can count
-// them: vector memory ops retire in issue order on gfx9, loads and stores alike.
-template <int UPD, int NS, int NK, int KL, class Issue>
-__device__ __forceinline__ void mlp_fused_dw1(const MlpArgs& a, const f4 (&wres)[NK - KL][4], const float* park, const float* Hs,
-                                              const float* stg, int rows, float* wrow, float* grow, float* mrow,
-                                              Issue& issue, int i0, int ipw) {
-  const int B = a.B, d = a.d, h = a.h;
-  const int hp = h + 4;
-  int lane = threadIdx.x & 63;
-  asm volatile("" : "+v"(lane));  // fresh lane-derived addresses: no CSE with F1's, held live across it
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 31, hh = lane >> 5;
-  const int64_t P = int64_t(h) * d + h + int64_t(a.c) * h + a.c;
-  const rsrc_t rW = make_rsrc(wrow, P * 4);
-  const rsrc_t rM = make_rsrc(UPD >= 2 ? mrow : wrow, UPD >= 2 ? P * 4 : 0);
-  const rsrc_t rG = make_rsrc(grow ? grow : wrow, grow ? P * 4 : 0);
-  float bz[16];  // B operand: dZ1[b = 2 s + hh][32 wave + li]
-#pragma unroll
-  for (int s = 0; s < 16; ++s) {
-    const int b = 2 * s + hh;
-    const float v = Hs[min(b, B - 1) * hp + 32 * wave + li];  // unconditional read, then select (no branch)
-    bz[s] = b < B ? v : 0.f;
-  }
-  const int sg = 16 * ((li >> 2) & 1) + 4 * (li >> 3) + (li & 3);  // sigma(li)
-  const int xp = sg >> 2, xe = sg & 3;                               // its 16-B piece, element
-  const int ipw_b1 = ipw - i0;                                       // DMA instructions per wave per chunk
-  constexpr int kSt = 12;                                            // 16-B stores per lane per tile
-  const uint32_t rowoff = uint32_t(((32 * wave + li) * d + 16 * hh) * 4);
-#pragma unroll
-  for (int dt = 0; dt < NK; ++dt) {
-    // ops issued after chunk dt's DMA: the next chunks' DMAs and the last tiles' stores
-    const int later = min(NS - 2, NK - 1 - dt) * ipw_b1 + min(dt, NS - 1) * kSt;
-    wait_vmcnt(min(later, 63));
-    __builtin_amdgcn_s_barrier();  // chunk dt landed for every wave; stage (dt - 1) % NS is free
-    if (dt + NS - 1 < NK) issue(dt + NS - 1, mrow, i0);
-    const float* st = stg + (dt % NS) * rows * 32;
-    float xv[16];  // A operand: X[b = 2 s + hh][32 dt + sigma(li)]
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int b = 2 * s + hh;  // < 32: always inside the staged X rows
-      const float v = st[(h + b) * 32 + ((xp ^ (b & 7)) * 4) + xe];
-      xv[s] = b < B ? v : 0.f;
-    }
-    f32x16 acc, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = acc1[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < 16; s += 2) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s], bz[s], acc, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[s + 1], bz[s + 1], acc1, 0, 0, 0);
-    }
-    acc += acc1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f4 mv = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (UPD == 3) mv = *reinterpret_cast<const f4*>(st + (32 * wave + li) * 32 + ((4 * hh + j) ^ (li & 7)) * 4);
-      const f4 w0 = dt < NK - KL ? wres[dt < NK - KL ? dt : 0][j]
-                                 : *reinterpret_cast<const f4*>(park + ((dt - (NK - KL)) * 16 + wave * 4 + j) * 256 + lane * 4);
-      f4 g, w, m;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float gg = acc[4 * j + q];
-        float dd = gg, mr = 0.f;
-        if constexpr (UPD == 2) {
-          mr = gg;
-        } else if constexpr (UPD == 3) {
-          mr = mv[q] * a.mom + gg;
-          dd = mr;
-        }
-        g[q] = gg;
-        m[q] = mr;
-        w[q] = __builtin_fmaf(a.neg_lr, dd, w0[q]);
-      }
-      const uint32_t vo = 32 * dt + 16 * hh + 4 * j < d ? rowoff + uint32_t((32 * dt + 4 * j) * 4) : kOOB;
-      bstore4(rG, vo, g);
-      bstore4(rW, vo, w);
-      bstore4(rM, vo, m);
-    }
-  }
-}
 
 // Per-agent part: forward, CE, backward down to dZ1 (-> ws[agent][b][h]),
 // updates of b1, W2, b2.
@@ -357,21 +245,17 @@ __device__ __forceinline__ void mlp_fused_dw1(const MlpArgs& a, const f4 (&wres)
 // deep; a row-contiguous load touches 8 lines per instruction where reading
 // the MFMA fragments straight from HBM touched 64 (2.3 TB/s effective).
 // NT = accumulator tiles per wave: 1 when h * ceil(B/32) <= 128, else 4.
-// PH (r03): 0 = the whole per-agent part in one kernel; 1 = F1 only, H (after
-// bias + relu) to ws[agent][b][h] (LDS = the F1 staging alone); 2 = the rest
-// (F2, CE, B2, dZ1 -> ws) from that H.  1 + 2 run the same operations in the
-// same order as 0 (bit-identical); the split lets F1 stream W1 without the
-// HBM-idle tail and with deeper staging.
-// PH 3 (r03): the whole step in one kernel for h = 128, B <= 32 and NK = d / 32
-// chunks known at compile time -- F1 keeps every W1 fragment it reads (NK x 16
-// floats per lane: the agent's 128 x d W1 lives in the CU's register file), so
-// B1 + the W1 update run on the resident W1 and W1 is read from HBM once, not
-// twice; see mlp_fused_dw1 above.  Bit-identical to 0 + mlp_dw1_kernel
-// (tests/test_mlp_gpu.py::test_step_paths_bit_identical), opt-in
-// (DOL_MLP_FUSED=1): see the measurement at the dispatch below.
-template <int NT, int UPD, bool TH, bool AL, int NS = kStages, int PH = 0, int NK = 0>
+//
+// The 48 kernels of this file are the ones a07f8d3 built for its default path,
+// instruction for instruction.  Their register allocation follows the order of
+// the optimizer's IR, and that order moved with each of these, so they stay as
+// a07f8d3 had them until the kernel's code changes for another reason: the
+// union offset written out in the body (not a call of fwd_union_floats), the
+// load_small and f1_chunk lambdas, issue()'s `top` and `i0` parameters (always
+// wrow and 0), the unused descriptor rsX, and the body / kernel pairs.
+template <int NT, int UPD, bool TH, bool AL>
 __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) {
-  static_assert(PH != 3 || (NT == 1 && NK > 0 && !TH && !AL && UPD >= 1), "fused step: plain / momentum SGD, one tile per wave");
+  constexpr int NS = kStages;
   if (a.stagger > 0) {
     const int bx = int(blockIdx.x);
     if (bx >= a.stagger_lo && bx < a.stagger_hi && (bx - a.stagger_lo) % a.stagger_step == 0)
@@ -380,12 +264,14 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int B = a.B, d = a.d, h = a.h, c = a.c;
   const int hp = h + 4;  // padded LDS rows: 16-B aligned, rows 4 banks apart
-  constexpr int KL = PH == 3 ? fused_park_chunks(NK, NS) : 0;
-  float* park = lds + fwd_staging_floats(B, h, NS);  // PH 3: [KL][4 waves][4 j][64 lanes] f4
-  float* Hs = lds + (PH == 3 ? fwd_staging_floats(B, h, NS) + 4096 * KL : 0);  // [B][hp]  H, later dZ1   (after F1)
+  const int64_t stg_rows = h + 32 * ((B + 31) / 32);  // rows of one F1 stage (128 B each)
+  float* Hs = lds;                   // [B][hp]  H, later dZ1   (after F1)
   float* W2s = Hs + B * hp;          // [c][hp]                 (after F1)
   float* Zs = W2s + c * hp;          // [B][c]   Z2, later dZ2
-  float* b1s = lds + fwd_union_floats(B, h, c, NS, PH == 3, KL);  // [h]
+  // past the union (= fwd_union_floats(B, h, c))
+  const int64_t stg_f = stg_rows * (32 * NS);
+  const int64_t post_f = int64_t(B) * (h + 4) + int64_t(c) * (h + 4) + int64_t(B) * c;
+  float* b1s = lds + (stg_f > post_f ? stg_f : post_f);  // [h]
   float* b2s = b1s + h;              // [c]
   float* ls = b2s + c;               // [B] per-sample loss
   int* ys = reinterpret_cast<int*>(ls + B);  // [B]
@@ -417,55 +303,25 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
     pb1.load(a, wrow, mrow, arow, idx_b1);
     pb2.load(a, wrow, mrow, arow, idx_b2);
   };
-  if constexpr (PH != 1) {
-    if constexpr (PH != 3) load_small();  // PH 3: after F1 (the registers hold W1 during F1)
-    if (t < c) b2s[t] = wrow[ob2 + t];
-    if (t < B) ys[t] = static_cast<int>(a.Y[int64_t(agent) * a.ldya + t]);
-  }
-  if constexpr (PH == 0 || PH == 3)
-    for (int i = t; i < h; i += kThreads) b1s[i] = wrow[ob1 + i];
-  if constexpr (PH != 1) lds_barrier();  // PH 1: the staging is the whole LDS (b1 read from memory below)
-  float* wsa = ws + int64_t(agent) * B * h;  // H (PH 1 -> 2), then dZ1 for mlp_dw1_kernel
+  load_small();
+  if (t < c) b2s[t] = wrow[ob2 + t];
+  if (t < B) ys[t] = static_cast<int>(a.Y[int64_t(agent) * a.ldya + t]);
+  for (int i = t; i < h; i += kThreads) b1s[i] = wrow[ob1 + i];
+  lds_barrier();
+  float* wsa = ws + int64_t(agent) * B * h;  // dZ1 for mlp_dw1_kernel
   // pw2 holds W2 itself when the update (or the prox term) loaded it and it fits one batch
   const bool w2_in_regs = (UPD > 0 || TH) && c * h <= 8 * kThreads;
   // ---- F1: Z1^T tiles (32 h x 32 b) on MFMA, K = d in chunks of 32
   const int nht = h / 32, nbt = (B + 31) / 32;
-  const int Bp = 32 * nbt, rows = PH == 3 ? 160 : h + Bp;  // staged rows per chunk (W1 rows, then X rows)
+  const int Bp = 32 * nbt, rows = h + Bp;  // staged rows per chunk (W1 rows, then X rows)
   const int ipw = rows / 32;               // DMA instructions per wave per chunk (8 rows each)
-  const int nk = NK > 0 ? NK : (d + 31) / 32;
+  const int nk = (d + 31) / 32;
   float* stg = lds;
-  // PH 3 stages through buffer descriptors: one 32-bit lane offset per staged
-  // row serves W1 and momentum alike (chunk kc in the SGPR offset), and the
-  // k >= d pieces of a tail chunk read as zeros (out-of-range lanes): few VGPRs
-  // beside the resident W1, no zeroing pass.
-  const int64_t P1 = int64_t(h) * d + h + int64_t(c) * h + c;
-  const rsrc_t rsW = make_rsrc(wrow, P1 * 4);
-  const rsrc_t rsM = make_rsrc(UPD == 3 && PH == 3 ? mrow : wrow, P1 * 4);
-  const rsrc_t rsX = make_rsrc(xa, (int64_t(B - 1) * a.ldxb + d) * 4);
-  uint32_t voff3[5];  // PH 3: per staged row group i (4 x W1 / momentum, 1 x X)
-  if constexpr (PH == 3) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int r = 8 * (wave + kWaves * i) + (lane >> 3);
-      const int ch = (lane & 7) ^ (lane >> 3);
-      voff3[i] = i < 4 ? uint32_t((r * d + 4 * ch) * 4) : uint32_t((min(r - h, B - 1) * a.ldxb + 4 * ch) * 4);
-    }
-  }
-  // stage chunk kc of rows [i0 * 32, rows) (W1 / momentum rows from `top`, then X)
+  const rsrc_t rsX = make_rsrc(xa, (int64_t(B - 1) * a.ldxb + d) * 4);  // unused (see above)
+  (void)rsX;
+  // stage chunk kc: rows [i0 * 32, rows) of the W1 rows from `top`, then the X rows
   auto issue = [&](int kc, const float* top, int i0) {
     float* st = stg + (kc % NS) * rows * 32;
-    if constexpr (PH == 3) {
-      const bool tail = kc == nk - 1 && (d & 31);  // (compile-time false before the last chunk)
-      const bool pok = 32 * kc + 4 * ((lane & 7) ^ (lane >> 3)) < d;
-#pragma unroll
-      for (int i = i0; i < 5; ++i) {
-        const uint32_t vo = !tail || pok ? voff3[i] : kOOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(i < 4 ? (top == wrow ? rsW : rsM) : rsX,
-                                                 DOL_LPTR(st + (wave + kWaves * i) * 256), 16, static_cast<int>(vo),
-                                                 kc * 128, 0, 0);
-      }
-      return;
-    }
     for (int i = i0; i < ipw; ++i) {
       const int ins = wave + kWaves * i;
       const int r = 8 * ins + (lane >> 3);
@@ -482,17 +338,6 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
         __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(st + ins * 256), 16, 0, 2);
     }
   };
-  // PH 3: W1[32 wave + li][32 kc + 16 hh + 4 j + q] = wres[kc][j][q] (the last KL chunks: park)
-  f4 wres[PH == 3 ? NK - KL : 1][4];
-  const int i0_b1 = UPD == 3 ? 0 : PH == 3 ? 4 : h / 32;  // PH 3's B1 chunks: momentum rows (UPD 3) + X rows, or X rows only
-  if constexpr (PH == 2) {  // H from the F1 kernel
-    if (w2_in_regs)
-      lds_fill<16>(B * h, [&](int o) { return wsa[o]; }, [&](int o, float v) { Hs[(o / h) * hp + (o % h)] = v; });
-    else
-      lds_fill2<16, 8>(B * h, [&](int o) { return wsa[o]; }, [&](int o, float v) { Hs[(o / h) * hp + (o % h)] = v; },
-                       c * h, [&](int o) { return wrow[oW2 + o]; }, [&](int o, float v) { W2s[(o / h) * hp + o % h] = v; });
-  } else {
-
   f32x16 acc[NT];
 #pragma unroll
   for (int u = 0; u < NT; ++u)
@@ -503,7 +348,7 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
     wait_vmcnt(min(NS - 2, nk - 1 - kc) * ipw);  // chunk kc landed (the next NS - 2 may still fly)
     __builtin_amdgcn_s_barrier();                 // ... for every wave; and stage (kc + NS - 1) % NS is free
     const float* st = stg + (kc % NS) * rows * 32;
-    if (PH != 3 && kc == nk - 1 && (d & 31)) {  // zero the clamped k >= d pieces of the tail chunk
+    if (kc == nk - 1 && (d & 31)) {  // zero the clamped k >= d pieces of the tail chunk
       for (int i = 0; i < ipw; ++i) {
         const int ins = wave + kWaves * i;
         if (kc * 32 + 4 * ((lane & 7) ^ (lane >> 3)) >= d)
@@ -524,28 +369,14 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
           const int pos = ((4 * hh + j) ^ (li & 7)) * 4;
           const f4 av = *reinterpret_cast<const f4*>(ar + pos);
           const f4 xv = *reinterpret_cast<const f4*>(xr + pos);
-          if constexpr (PH == 3) {
-            if (kc < NK - KL) wres[kc < NK - KL ? kc : 0][j] = av;
-            else *reinterpret_cast<f4*>(park + ((kc - (NK - KL)) * 16 + wave * 4 + j) * 256 + lane * 4) = av;
-          }
 #pragma unroll
           for (int q = 0; q < 4; ++q) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], xv[q], acc[u], 0, 0, 0);
         }
       }
     }
   };
-  if constexpr (PH == 3) {
-#pragma unroll
-    for (int kc = 0; kc < NK; ++kc) f1_chunk(kc);
-  } else {
-    for (int kc = 0; kc < nk; ++kc) f1_chunk(kc);
-  }
-  lds_barrier();  // staging is dead: Hs / W2s / Zs reuse it (PH 3: the momentum / X chunks of B1 start landing)
-  // PH 3: B1's first NS - 1 chunks (momentum rows when UPD == 3, then X) fly during F2 .. B2
-  if constexpr (PH == 3) {
-    load_small();
-    for (int s0 = 0; s0 < NS - 1 && s0 < NK; ++s0) issue(s0, mrow, i0_b1);
-  }
+  for (int kc = 0; kc < nk; ++kc) f1_chunk(kc);
+  lds_barrier();  // staging is dead: Hs / W2s / Zs reuse it
   // C/D map: col (b) = lane & 31, row (h) = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
   for (int u = 0; u < NT; ++u) {
@@ -557,21 +388,17 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int hr = 32 * ht + (r & 3) + 8 * (r >> 2) + 4 * hh;
-          const float z = acc[u][r] + (PH == 1 ? wrow[ob1 + hr] : b1s[hr]);
-          const float hz = (z > 0.0f || z != z) ? z : 0.0f;  // relu, NaN propagates like torch
-          if constexpr (PH == 1) wsa[brow * h + hr] = hz;
-          else Hs[brow * hp + hr] = hz;
+          const float z = acc[u][r] + b1s[hr];
+          Hs[brow * hp + hr] = (z > 0.0f || z != z) ? z : 0.0f;  // relu, NaN propagates like torch
         }
       }
     }
   }
-  if constexpr (PH == 1) return;
-  }  // PH != 2
   if (w2_in_regs) {  // W2 from the update operands loaded at the start: no memory round trip here
 #pragma unroll
     for (int i = 0; i < 8; ++i)
       if (ok_w2(i)) W2s[((i * kThreads + t) / h) * hp + (i * kThreads + t) % h] = pw2.w[i];
-  } else if constexpr (PH != 2) {  // (PH 2 filled W2s together with H)
+  } else {
     lds_fill<8>(c * h, [&](int o) { return wrow[oW2 + o]; }, [&](int o, float v) { W2s[(o / h) * hp + o % h] = v; });
   }
   lds_barrier();
@@ -716,125 +543,17 @@ __device__ __forceinline__ void mlp_fwd_body(MlpArgs a, float* __restrict__ ws) 
     pb1.commit(a, wrow, grow, mrow, g, idx_b1, ok_b1);
   }
 
-  if constexpr (PH == 3) {
-    DOL_TRACE(3)
-    lds_barrier();  // dZ1 complete in Hs
-    mlp_fused_dw1<UPD, NS, NK, KL>(a, wres, park, Hs, stg, rows, wrow, grow, mrow, issue, i0_b1, ipw);
-    DOL_TRACE(4)
-    return;
-  }
   // dZ1 for the W1 tiles of mlp_dw1_kernel
   for (int o = t; o < B * h; o += kThreads) wsa[o] = Hs[(o / h) * hp + (o % h)];
   DOL_TRACE(3)
 }
 
-template <int NT, int UPD, bool TH, bool AL, int NS = kStages, int PH = 0, int NK = 0>
-__global__ __launch_bounds__(kThreads) void mlp_fwd_kernel(MlpArgs a, float* __restrict__ ws) {
-  mlp_fwd_body<NT, UPD, TH, AL, NS, PH, NK>(a, ws);
-}
-
-// the per-agent tail (PH 2) compiled for four waves per SIMD (<= 128 VGPRs,
-// r04): at the default three (151 VGPRs) 1024 agents ran as two rounds of
-// 768 + 256 workgroups (tools/mlp_phase.hip 't')
 template <int NT, int UPD, bool TH, bool AL>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void mlp_tail_kernel(
-    MlpArgs a, float* __restrict__ ws) {
-  mlp_fwd_body<NT, UPD, TH, AL, 1, 2, 0>(a, ws);
+__global__ __launch_bounds__(kThreads) void mlp_fwd_kernel(MlpArgs a, float* __restrict__ ws) {
+  mlp_fwd_body<NT, UPD, TH, AL>(a, ws);
 }
 
-// F1 as one single-wave workgroup per (agent, 32-row h-tile), B <= 32 (r04):
-// H[:, 32 ht .. 32 ht + 32) = relu(W1[32 ht ..] X^T + b1) -> ws[agent][b][h],
-// then mlp_fwd_kernel PH 2 runs the per-agent tail from ws.  The per-agent F1
-// (4 waves, 61 KiB of staging, 2 workgroups per CU) streamed at 4.6 TB/s and
-// sat in lock step with the HBM-idle tail; here each wave owns its own
-// NS-deep LDS-DMA ring (W1 rows 0..31, X rows 32..63 of each 32-wide k chunk,
-// 16-B pieces swizzled by row as in mlp_fwd_kernel), no barriers, 8 KiB per
-// stage, so 4 - 5 independent rings share a CU.  X is fetched once per h-tile:
-// the nht tiles of an agent run on one XCD (blockIdx % 8 = agent % 8, tiles
-// consecutive), so the repeats meet in its L2.  Tail chunk pieces with k >= d
-// are out-of-range buffer lanes: they land as zeros, as mlp_fwd_kernel zeroes
-// them.  The MFMA sequence of a tile is the per-agent kernel's (same k order,
-// same operands): bit-identical H.
-// KW (k chunk width): 32 = 128-B row pieces, 8 rows per DMA instruction; 64 =
-// 256-B pieces, 4 rows per instruction, each 64-wide chunk consumed as two
-// 32-wide halves in k order (a half wholly past d is skipped, as the 32-wide
-// kernel never stages it): the same MFMA sequence either way.
-template <int NS, int KW = 32>
-__global__ __launch_bounds__(64) void mlp_f1_tile_kernel(MlpArgs a, float* __restrict__ ws, int n_agents) {
-  static_assert(KW == 32 || KW == 64, "k chunk: 32 or 64 floats");
-  constexpr int PPR = KW / 4;     // 16-B pieces per staged row (slot = piece ^ (row % PPR))
-  constexpr int RPI = 64 / PPR;   // staged rows per DMA instruction
-  constexpr int NI = 64 / RPI;    // DMA instructions per stage (64 staged rows)
-  __shared__ __attribute__((aligned(16))) float stg[NS * 64 * KW];
-  const int B = a.B, d = a.d, h = a.h;
-  const int nht = h / 32;
-  const uint32_t bx = blockIdx.x, l = bx >> 3;
-  const int ht = static_cast<int>(l % uint32_t(nht));
-  const int agent = static_cast<int>((l / uint32_t(nht)) * 8 + (bx & 7));
-  if (agent >= n_agents) return;
-  const int lane = threadIdx.x;
-  const int li = lane & 31, hh = lane >> 5;
-  const float* wrow = a.W + int64_t(agent) * a.ldw;
-  const int64_t P1 = int64_t(h) * d + h + int64_t(a.c) * h + a.c;
-  const rsrc_t rsW = make_rsrc(wrow, P1 * 4);
-  const rsrc_t rsX = make_rsrc(a.X + int64_t(agent) * a.ldxa, (int64_t(B - 1) * a.ldxb + d) * 4);
-  const int nk = (d + KW - 1) / KW;
-  // staged row r = RPI i + lane / PPR: W1 row 32 ht + r (r < 32), X row min(r - 32, B - 1) (r >= 32);
-  // lane's LDS slot lane % PPR holds piece slot ^ (r % PPR)
-  uint32_t voff[NI];
-  int pc[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int r = RPI * i + lane / PPR;
-    pc[i] = (lane % PPR) ^ (r % PPR);
-    voff[i] = r < 32 ? uint32_t(((32 * ht + r) * d + 4 * pc[i]) * 4) : uint32_t((min(r - 32, B - 1) * a.ldxb + 4 * pc[i]) * 4);
-  }
-  auto issue = [&](int kc) {
-    float* st = stg + (kc % NS) * 64 * KW;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(RPI * i < 32 ? rsW : rsX, DOL_LPTR(st + i * 256), 16,
-                                               static_cast<int>(KW * kc + 4 * pc[i] < d ? voff[i] : kOOB), kc * KW * 4,
-                                               0, 0);
-  };
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  for (int s0 = 0; s0 < NS - 1 && s0 < nk; ++s0) issue(s0);
-  for (int kc = 0; kc < nk; ++kc) {
-    wait_vmcnt(min(NS - 2, nk - 1 - kc) * NI);             // chunk kc landed (the next NS - 2 may still fly)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // last chunk's LDS reads done: its stage is free
-    if (kc + NS - 1 < nk) issue(kc + NS - 1);
-    const float* st = stg + (kc % NS) * 64 * KW;
-    const float* ar = st + li * KW;
-    const float* xr = st + (32 + li) * KW;
-#pragma unroll
-    for (int h2 = 0; h2 < KW / 32; ++h2) {
-      if (h2 > 0 && KW * kc + 32 * h2 >= d) break;  // a half wholly past d (wave-uniform)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int pos = ((8 * h2 + 4 * hh + j) ^ (li % PPR)) * 4;
-        const f4 av = *reinterpret_cast<const f4*>(ar + pos);
-        const f4 xv = *reinterpret_cast<const f4*>(xr + pos);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q], xv[q], acc, 0, 0, 0);
-      }
-    }
-  }
-  // C/D map: col (b) = lane & 31, row (h) = (r&3) + 8*(r>>2) + 4*(lane>>5); bias + relu as mlp_fwd_kernel PH 1
-  if (li < B) {
-    float* wsa = ws + int64_t(agent) * B * h;
-    const int64_t ob1 = int64_t(h) * d;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int hr = 32 * ht + (r & 3) + 8 * (r >> 2) + 4 * hh;
-      const float z = acc[r] + wrow[ob1 + hr];
-      wsa[li * h + hr] = (z > 0.0f || z != z) ? z : 0.0f;
-    }
-  }
-}
-
-// B1 + W1 update: block agent * ndt + dt owns columns [32 dt, 32 dt + 32) of W1
+// B1 + W1 update: one block owns columns [32 dt, 32 dt + 32) of one agent's W1
 // for all h rows; wave w takes h-tiles w, w + 4, ...  A = dZ1^T from the
 // workspace (L2), B = X[:, cols].  Memory goes through wave-uniform buffer
 // descriptors: one 32-bit lane offset per tile, the row step of each of the
@@ -842,31 +561,26 @@ __global__ __launch_bounds__(64) void mlp_f1_tile_kernel(MlpArgs a, float* __res
 // (loads return 0, stores are dropped), and every load of the tile issued
 // before the MFMA chain (sched_barrier) so the W1 / momentum reads overlap it.
 // KS = MFMA k-steps (2 samples each): 16 for B <= 32, 32 for B <= 64.
-// (buffer helpers: above mlp_fused_dw1)
-
-// XG (r04): XCD-grouped tile order.  With d = 784 a W1 row is 24.5 lines, so
+//
+// Tile order (r04): XCD-grouped.  With d = 784 a W1 row is 24.5 lines, so
 // the 128-B column piece of every odd row straddles two lines that the
 // neighbouring tile (dt +- 1) shares; the dispatcher deals consecutive blocks
 // to different XCDs, so with blockIdx = agent * ndt + dt both XCDs fetched
-// (and partially wrote back) those lines.  XG = 1 keeps every tile of an
-// agent on ONE XCD (blockIdx % 8 = agent % 8, tiles in order), so the shared
-// lines meet in that XCD's L2.  Same arithmetic per tile: same bits.
-template <int KS, int UPD, bool TH, bool AL, int CH = 1, int XG = 0>
+// (and partially wrote back) those lines.  Here every tile of an agent runs
+// on ONE XCD (blockIdx % 8 = agent % 8, tiles in order), so the shared lines
+// meet in that XCD's L2: 0.478-0.482 vs 0.506-0.507 ms agent-major
+// (profiles/r04e_mlp_dw1_xcd_ab.txt).  The grid is padded to a multiple of 8
+// agents; the blocks past n_agents return at once.
+template <int KS, int UPD, bool TH, bool AL>
 __device__ __forceinline__ void mlp_dw1_body(MlpArgs a, const float* __restrict__ ws, int n_agents) {
   const int B = a.B, d = a.d, h = a.h, c = a.c;
   const int ndt = (d + 31) / 32;
-  int dt, agent;
-  if constexpr (XG) {
-    const uint32_t b = blockIdx.x, l = b >> 3;
-    dt = static_cast<int>(l % uint32_t(ndt));
-    uint32_t lg = l / uint32_t(ndt);
-    if (a.dw1_reverse) lg = uint32_t((n_agents + 7) / 8) - 1 - lg;  // last agents first, each on its forward's XCD
-    agent = static_cast<int>(lg * 8 + (b & 7));
-    if (agent >= n_agents) return;
-  } else {
-    dt = static_cast<int>(blockIdx.x % ndt);
-    agent = static_cast<int>(blockIdx.x / ndt);
-  }
+  const uint32_t bx = blockIdx.x, l = bx >> 3;
+  const int dt = static_cast<int>(l % uint32_t(ndt));
+  uint32_t lg = l / uint32_t(ndt);
+  if (a.dw1_reverse) lg = uint32_t((n_agents + 7) / 8) - 1 - lg;  // last agents first, each on its forward's XCD
+  const int agent = static_cast<int>(lg * 8 + (bx & 7));
+  if (agent >= n_agents) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int li = lane & 31, hh = lane >> 5;
@@ -907,18 +621,17 @@ __device__ __forceinline__ void mlp_dw1_body(MlpArgs a, const float* __restrict_
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if constexpr (CH == 2) {  // two independent k-chains (even / odd k-steps), summed at the end
-      f32x16 acc1 = acc;
+    // two independent k-chains (even / odd k-steps), summed at the end (VERDICT r02
+    // item 4): 0.5036-0.5046 vs 0.5074-0.5079 ms with one chain, three alternating
+    // pairs on one box (profiles/r03_mlp_dw1_chains.txt) -- the step is not
+    // chain-latency bound.  One chain rounds differently (1 ulp of W1).
+    f32x16 acc1 = acc;
 #pragma unroll
-      for (int s = 0; s < KS; s += 2) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], xv[s], acc, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s + 1], xv[s + 1], acc1, 0, 0, 0);
-      }
-      acc += acc1;
-    } else {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], xv[s], acc, 0, 0, 0);
+    for (int s = 0; s < KS; s += 2) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], xv[s], acc, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s + 1], xv[s + 1], acc1, 0, 0, 0);
     }
+    acc += acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float gg = acc[r];
@@ -941,17 +654,9 @@ __device__ __forceinline__ void mlp_dw1_body(MlpArgs a, const float* __restrict_
   }
 }
 
-template <int KS, int UPD, bool TH, bool AL, int CH = 1, int XG = 0>
+template <int KS, int UPD, bool TH, bool AL>
 __global__ __launch_bounds__(kThreads) void mlp_dw1_kernel(MlpArgs a, const float* __restrict__ ws, int n_agents) {
-  mlp_dw1_body<KS, UPD, TH, AL, CH, XG>(a, ws, n_agents);
-}
-
-// dW1 compiled for four waves per SIMD (<= 128 VGPRs + AGPRs; DOL_MLP_DW1_OCC=4):
-// the two-chain kernel needs 98 + 32 and runs three
-template <int KS, int UPD, bool TH, bool AL, int CH, int XG>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void mlp_dw1_occ4_kernel(
-    MlpArgs a, const float* __restrict__ ws, int n_agents) {
-  mlp_dw1_body<KS, UPD, TH, AL, CH, XG>(a, ws, n_agents);
+  mlp_dw1_body<KS, UPD, TH, AL>(a, ws, n_agents);
 }
 
 }  // namespace
@@ -1035,137 +740,24 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
   const size_t lds = static_cast<size_t>(dol_mlp_step_lds_bytes(B, h, c));
   if (lds > 160 * 1024) return fail(DOL_EINVAL, "dol_mlp_step_f32: %zu B of LDS per agent exceeds 160 KiB", lds);
   const dim3 grid(static_cast<unsigned>(n_agents)), block(kThreads);
-  // F1 pipeline depth (DOL_MLP_STAGES = 2 / 3 / 4; diagnostics, default 3)
-  static const int stages = [] { const char* e = getenv("DOL_MLP_STAGES"); return e ? atoi(e) : kStages; }();
-  // forward as two kernels (F1 / the per-agent tail; bit-identical), opt-in with
-  // DOL_MLP_SPLIT_FWD=1: measured 0.518-0.524 (F1 depth 3 / 4) and 0.509-0.511
-  // (depth 2) vs 0.509-0.513 ms fused (profiles/r03_mlp_split_fwd.txt)
-  static const int split_fwd = [] { const char* e = getenv("DOL_MLP_SPLIT_FWD"); return e ? atoi(e) : 0; }();
-  // F1 as single-wave (agent, h-tile) workgroups with NS-deep rings (mlp_f1_tile_kernel;
-  // DOL_MLP_F1_TILES = NS in {3, 4, 5, 6, 8}, 0 = off), B <= 32
-  static const int f1_tile_ns = [] { const char* e = getenv("DOL_MLP_F1_TILES"); return e ? atoi(e) : 0; }();
-  // its k chunk width (DOL_MLP_F1_KW = 32 / 64; 64 takes NS 3 or 4) and the
-  // tail's occupancy (DOL_MLP_TAIL_OCC = 4: mlp_tail_kernel, <= 128 VGPRs)
-  static const int f1_kw = [] { const char* e = getenv("DOL_MLP_F1_KW"); return e ? atoi(e) : 32; }();
-  static const int tail_occ4 = [] { const char* e = getenv("DOL_MLP_TAIL_OCC"); return e ? atoi(e) == 4 : 0; }();
   const int upd = update ? mode + 1 : 0;
   float* ws = static_cast<float*>(work);
-  // dW1 tile order (DOL_MLP_DW1_XCD: 1 = an agent's tiles on one XCD, 0 = agent-major)
-  static const int dw1_xcd = [] { const char* e = getenv("DOL_MLP_DW1_XCD"); return e ? atoi(e) : 1; }();
-  const int64_t n_blk2 = int64_t((d + 31) / 32) * (dw1_xcd ? (int64_t(n_agents) + 7) / 8 * 8 : n_agents);
+  // dW1: every 32-column tile of 8 agents at a time (XCD-grouped, see mlp_dw1_kernel)
+  const int64_t n_blk2 = int64_t((d + 31) / 32) * ((int64_t(n_agents) + 7) / 8 * 8);
   if (n_blk2 > (int64_t(1) << 31) - 1) return fail(DOL_EINVAL, "dol_mlp_step_f32: too many W1 tiles for one launch");
   const dim3 grid2(static_cast<unsigned>(n_blk2));
-  // dW1's k-chain as two interleaved accumulators summed at the end (VERDICT r02
-  // item 4): local step 0.5036-0.5046 vs 0.5074-0.5079 ms with one chain, three
-  // alternating pairs on one box (profiles/r03_mlp_dw1_chains.txt) -- the step
-  // is not chain-latency bound.  DOL_MLP_DW1_CHAINS=1 used to restore one chain;
-  // one fma chain rounds differently from two (1 ulp of W1, 1.5e-8 at 784-128-10:
-  // tests/test_mlp_gpu.py::test_step_paths_bit_identical), so it was never the
-  // "same bits" A/B switch it was used as: the setting is refused with a message
-  // and the step runs the two-chain kernels, like every other path.
-  static const int dw1_chains = [] {
-    const char* e = getenv("DOL_MLP_DW1_CHAINS");
-    if (e && atoi(e) != 2)
-      fprintf(stderr, "dol_mlp_step_f32: DOL_MLP_DW1_CHAINS=%s ignored: a one-chain dW1 does not give the default's "
-                      "bits; running two chains\n", e);
-    return 2;
-  }();
-  static const int dw1_occ4 = [] { const char* e = getenv("DOL_MLP_DW1_OCC"); return e ? atoi(e) == 4 : 0; }();
-  // diagnostics: unused dynamic LDS per dW1 workgroup, to cap its occupancy (DOL_MLP_DW1_LDS bytes, <= 64 KiB)
-  static const size_t dw1_lds = [] {
-    const char* e = getenv("DOL_MLP_DW1_LDS");
-    const long v = e ? atol(e) : 0;
-    return static_cast<size_t>(v < 0 ? 0 : v > 65536 ? 65536 : v);
-  }();
-  // the one-kernel step with W1 resident in registers (mlp_fwd_kernel PH 3;
-  // DOL_MLP_FUSED=1).  It reads W1 once (1.75 instead of 2.16 GB per step at 1024
-  // agents) but its 400 resident floats per lane leave one workgroup per CU:
-  // per agent F1 27-42 us (latency-bound at 4 chunks in flight), F2 + CE 6 and
-  // B2 20 (HBM nearly idle) and B1 66-74 us, 0.588 ms in all vs 0.56 for the two
-  // kernels in the same tool (tools/mlp_phase.hip, profiles/r03_mlp_fused.txt):
-  // kept opt-in.
-  static const int fused = [] { const char* e = getenv("DOL_MLP_FUSED"); return e ? atoi(e) : 0; }();
-  const bool a16 = !(reinterpret_cast<uintptr_t>(mom) & 15) && ldm % 4 == 0 && !(reinterpret_cast<uintptr_t>(grad) & 15) &&
-                   ldg % 4 == 0;
-  const int nkc = (d + 31) / 32;
-  const bool fusable = fused && h == 128 && B <= 32 && a16 && (nkc == 25 || nkc == 4);
   auto go = [&](auto ks, auto upd_c, auto th, auto al) {
     constexpr int KS = decltype(ks)::value, U = decltype(upd_c)::value;
     constexpr bool TH = decltype(th)::value, AL = decltype(al)::value;
-    auto fwd = [&](auto kern, size_t lds_ns) {
-      if (lds_ns > 65536)  // above the default dynamic-LDS cap (gfx950 has 160 KiB per CU)
+    auto fwd = [&](auto kern) {
+      if (lds > 65536)  // above the default dynamic-LDS cap (gfx950 has 160 KiB per CU)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds_ns));
-      hipLaunchKernelGGL(kern, grid, block, lds_ns, s, a, ws);
+                                  static_cast<int>(lds));
+      hipLaunchKernelGGL(kern, grid, block, lds, s, a, ws);
     };
-    auto lds_for = [&](int ns) {
-      return sizeof(float) * (fwd_union_floats(B, h, c, ns) + h + c + B) + sizeof(int) * size_t(B);
-    };
-    const bool nt1 = h * ((B + 31) / 32) <= 128;
-    if constexpr (!TH && !AL && U >= 1 && KS == 16) {
-      if (fusable) {
-        auto fz = [&](auto nk_c, auto ns_c) {
-          constexpr int NK = decltype(nk_c)::value, NS = decltype(ns_c)::value;
-          fwd(mlp_fwd_kernel<1, U, false, false, NS, 3, NK>,
-              sizeof(float) * (fwd_union_floats(B, h, c, NS, true, fused_park_chunks(NK, NS)) + h + c + B) +
-                  sizeof(int) * size_t(B));
-        };
-        if (nkc == 25) fz(std::integral_constant<int, 25>{}, std::integral_constant<int, 5>{});
-        else fz(std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});
-        return;
-      }
-    }
-    // the per-agent tail (PH 2) needs no F1 staging: LDS = its post-F1 arrays alone
-    auto tail = [&] {
-      if (tail_occ4) {
-        if (nt1) fwd(mlp_tail_kernel<1, U, TH, AL>, lds_for(1));
-        else fwd(mlp_tail_kernel<4, U, TH, AL>, lds_for(1));
-      } else if (nt1) {
-        fwd(mlp_fwd_kernel<1, U, TH, AL, 1, 2>, lds_for(1));
-      } else {
-        fwd(mlp_fwd_kernel<4, U, TH, AL, 1, 2>, lds_for(1));
-      }
-    };
-    if (f1_tile_ns && B <= 32 && P * 4 < (int64_t(1) << 31)) {  // F1 per (agent, h-tile), then the tail
-      const dim3 gt(static_cast<unsigned>(int64_t(h / 32) * ((int64_t(n_agents) + 7) / 8 * 8))), bt(64);
-      if (f1_kw == 64) {
-        if (f1_tile_ns == 4) hipLaunchKernelGGL((mlp_f1_tile_kernel<4, 64>), gt, bt, 0, s, a, ws, n_agents);
-        else hipLaunchKernelGGL((mlp_f1_tile_kernel<3, 64>), gt, bt, 0, s, a, ws, n_agents);
-      } else if (f1_tile_ns == 3) hipLaunchKernelGGL(mlp_f1_tile_kernel<3>, gt, bt, 0, s, a, ws, n_agents);
-      else if (f1_tile_ns == 4) hipLaunchKernelGGL(mlp_f1_tile_kernel<4>, gt, bt, 0, s, a, ws, n_agents);
-      else if (f1_tile_ns == 6) hipLaunchKernelGGL(mlp_f1_tile_kernel<6>, gt, bt, 0, s, a, ws, n_agents);
-      else if (f1_tile_ns == 8) hipLaunchKernelGGL(mlp_f1_tile_kernel<8>, gt, bt, 0, s, a, ws, n_agents);
-      else hipLaunchKernelGGL(mlp_f1_tile_kernel<5>, gt, bt, 0, s, a, ws, n_agents);
-      tail();
-    } else if (split_fwd) {  // F1 kernel (staging only in LDS), then the per-agent tail kernel
-      auto f1 = [&](auto ns_c) {
-        constexpr int NS = decltype(ns_c)::value;
-        const size_t l1 = sizeof(float) * size_t(NS) * (h + 32 * ((B + 31) / 32)) * 32;
-        if (nt1) fwd(mlp_fwd_kernel<1, U, TH, AL, NS, 1>, l1);
-        else fwd(mlp_fwd_kernel<4, U, TH, AL, NS, 1>, l1);
-      };
-      if (stages == 2) f1(std::integral_constant<int, 2>{});
-      else if (stages == 4) f1(std::integral_constant<int, 4>{});
-      else if (stages == 5) f1(std::integral_constant<int, 5>{});
-      else f1(std::integral_constant<int, 3>{});
-      tail();
-    } else if (stages == 2) {
-      if (nt1) fwd(mlp_fwd_kernel<1, U, TH, AL, 2>, lds_for(2));
-      else fwd(mlp_fwd_kernel<4, U, TH, AL, 2>, lds_for(2));
-    } else if (stages == 4 && lds_for(4) <= 160 * 1024) {
-      if (nt1) fwd(mlp_fwd_kernel<1, U, TH, AL, 4>, lds_for(4));
-      else fwd(mlp_fwd_kernel<4, U, TH, AL, 4>, lds_for(4));
-    } else {
-      if (nt1) fwd(mlp_fwd_kernel<1, U, TH, AL>, lds);
-      else fwd(mlp_fwd_kernel<4, U, TH, AL>, lds);
-    }
-    (void)dw1_chains;  // always 2 (see above)
-    if (dw1_xcd && dw1_occ4)
-      hipLaunchKernelGGL((mlp_dw1_occ4_kernel<KS, U, TH, AL, 2, 1>), grid2, block, 0, s, a, ws, n_agents);
-    else if (dw1_xcd)
-      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 2, 1>), grid2, block, dw1_lds, s, a, ws, n_agents);
-    else
-      hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL, 2>), grid2, block, 0, s, a, ws, n_agents);
+    if (h * ((B + 31) / 32) <= 128) fwd(mlp_fwd_kernel<1, U, TH, AL>);  // one accumulator tile per wave
+    else fwd(mlp_fwd_kernel<4, U, TH, AL>);
+    hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL>), grid2, block, 0, s, a, ws, n_agents);
   };
   auto by_upd = [&](auto ks, auto th, auto al) {
     using std::integral_constant;

@@ -1,7 +1,7 @@
 """The fused MLP step's dispatch matrix (csrc/mlp_step.hip) against the fp64
 reference of the whole step (oracle/mlp_ref.py): every update template
 (plain / prox / ADMM x SGD / first momentum step / momentum x grad written or
-not) at the shapes where mlp_fwd_body and the dW1 kernels take another branch,
+not) at the shapes where mlp_fwd_kernel and mlp_dw1_kernel take another branch,
 the ABI edges of dol_mlp_step_f32 (strided X, strided labels, no loss,
 rows= slices), and the launch geometry at and above the forward's stagger
 threshold (4 n_cu agents), where config 5 runs.
@@ -17,20 +17,16 @@ Which test reaches which path of mlp_step.hip:
   KS = 32 with UPD >= 1 test_step_matrix_matches_fp64[3-33-100-96-17 / 2-64-36-64-3 / 2-64-40-256-32]
   TH / AL x mode 0 / 1 / 2 x write_grad
                         test_step_matrix_matches_fp64[*-prox-* / *-admm-*]
-  TH / AL on the tail, split forward, F1 tiles, dW1 occ4
-                        test_mlp_gpu.py::test_step_paths_bit_identical (prox / ADMM cases),
-                        pinned by test_mlp_gpu.py::test_base_step_child_matches_fp64
   w2_in_regs == false under an update
                         test_step_matrix_matches_fp64[2-64-40-256-32 / 2-8-4-224-10]
-  lds_fill2's split fallback (the tail kernels at c h > 2048)
-                        test_mlp_gpu.py::test_step_paths_bit_identical, case (2, 8, 4, 224, 10)
   kThreads % h != 0     test_step_matrix_matches_fp64[3-33-100-96-17 / 2-8-4-224-*]
   B h > 16 kThreads     test_step_matrix_matches_fp64[2-64-40-256-32]
   mode 1 ignores mom    test_step_matrix_matches_fp64[*-0.5-*] (mom starts as NaN)
   DOL_MLP_FWD_STAGGER "0" / mode 2
                         test_small_rows_every_agent_above_the_stagger_threshold
-  the other DOL_MLP_* switches
-                        test_mlp_gpu.py::test_step_paths_bit_identical
+  DOL_MLP_F1_KEEP=0, DOL_MLP_DW1_REVERSE=0
+                        test_mlp_gpu.py::test_step_paths_bit_identical,
+                        pinned by test_mlp_gpu.py::test_base_step_child_matches_fp64
   ldx_row > d, padded agent stride / ldy_agent > B / loss = NULL / rows=
                         test_padded_x_rows_and_agent_stride, test_labels_as_a_column_view,
                         test_step_without_a_loss_buffer, test_rows_slice_steps_only_its_agents,

@@ -1,9 +1,9 @@
 """Config 5's fused MLP local step (1024 agents x 784-128-10, B = 32,
 momentum 0.5) under settings of one environment variable the step reads per
-call (--var, e.g. DOL_MLP_DW1_PAIR), alternating in one process; the updated
+call (--var, e.g. DOL_MLP_FWD_STAGGER), alternating in one process; the updated
 rows and momentum compared bit for bit against the first setting's step from
 the same start.  One JSON line per (trial, setting).
-  python tools/mlp_env_ab.py --var DOL_MLP_DW1_PAIR --settings 0 1 [--reps 50]"""
+  python tools/mlp_env_ab.py --var DOL_MLP_FWD_STAGGER --settings 0 6,1 [--reps 50]"""
 import argparse
 import json
 import os
