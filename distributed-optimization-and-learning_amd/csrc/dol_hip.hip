@@ -10,6 +10,29 @@
 // with leading dimension ld (elements).  Columns are streamed 16 B per lane
 // (f4) when every row base is 16-B aligned; otherwise, and for the
 // P % 4 tail, the same kernels run on scalar columns.
+//
+// This file holds the default paths only.  Launch variants of the ring, CSR
+// and ADMM kernels that were measured behind environment switches and dropped
+// (8192 x 2^20 unless noted; all gave the default's bits unless noted; none
+// was consistently faster; code last present at 1a824fc):
+//   DOL_RING_DMA=0, DOL_RING_PF / _NT / _ROWS: the float4 ring mix staged in registers
+//     (ring_mix_kernel<f4, ...>), 5.91 vs 6.17 TB/s for the LDS-DMA kernel; R = 64 tiles 5.1-5.4.
+//   DOL_RING_NTI=0: the LDS-DMA ring mix without nontemporal interior-row loads,
+//     11.15-11.16 vs 10.90-10.93 ms (profiles/r01d_ring_nti.txt).
+//   DOL_CSR_PASSES=1|4: csr_xcd_kernel with 8 / 32 rows per block instead of 16: 512-B tiles 17.94 ms
+//     with 1 pass vs 17.01 with 2; 256-B tiles 18.99 with 4 vs 18.52 (profiles/r01_membench6_csr.txt).
+//   DOL_RING_STREAM=1 as a process default, DOL_RING_STREAM_T / _PF / _NT / _LDS: ring_stream_kernel with 4 / 16
+//     rows in flight, plain loads, other tile heights, an LDS occupancy cap (profiles/r03_eps_stream.txt; see
+//     dol_mix_ring_steps_ex_f32 for the box A / C / E figures).  The kernel stays as variant 2.
+//   DOL_RING_DMA_D=16: ring_stream_dma_kernel with a 16-row ring per wave, 12.53 vs 12.61 ms at 1024-row
+//     tiles, 12.86 vs 12.81 at 8192 (profiles/r04c_eps_dma_sweep.jsonl).  DOL_RING_DMA_SYNC / _ORDER: variants 4 / 5.
+//   DOL_RING_DMA_PROBE=1: that kernel as a copy (wrong results by design), as fast as the real one,
+//     12.59 vs 12.61 ms: the pass is bound by its access pattern (same file).
+//   DOL_ADMM_ROUND_THREADS: admm_ls_round_mean_kernel strips forced to 1024 / 256 / 64 lanes; at 8192 x 2^17
+//     18.6 / 7.4 / 7.65 ms, and 5.15 for the two-kernel round (profiles/r06c_admm_narrow_ab.jsonl).
+// Switches that stay: DOL_CSR_MODE (both kernels it selects are live under the automatic rule),
+// DOL_DGD_EPI_NT (a runtime branch inside every DGD kernel), DOL_BANK_* (tested behaviour), and
+// dol_ring_steps_set_variant / variants 1-5 of dol_mix_ring_steps_ex_f32 (the product path's tuner picks).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -144,7 +167,8 @@ struct DgdEpi {
   // at 1024 x 2^20, least squares + momentum) and ran 3.58-3.59 ms; with these
   // 12.90 GB = 1.00x and 3.44-3.45 ms (profiles/r06f_dgd_epi_policy.jsonl; sc0
   // sc1 without nt: no change).  DOL_DGD_EPI_NT=0 restores plain loads, 1 the
-  // compiler's nontemporal global loads.
+  // compiler's nontemporal global loads (the switch stays: it is this runtime
+  // branch, inside every DGD kernel).
   int nt;
 
   template <typename V> __device__ __forceinline__ V ld(const float* row, int64_t cf) const {
@@ -209,17 +233,21 @@ __device__ __forceinline__ void stv(V* p, V v) {
 }
 
 // ----------------------------------------------------------------------------
-// Ring mix: one workgroup = one column tile (256 lanes x V = 4 KiB of a row)
-// x R consecutive agent rows.  The three-point stencil along the agent axis is
-// carried in a register window; PF rows are loaded one iteration ahead.
+// Ring mix, register-staged: one workgroup = one column tile (256 lanes x V)
+// x rows_per_block consecutive agent rows.  The three-point stencil along the
+// agent axis is carried in a register window; PF rows are loaded one iteration
+// ahead.  Runs the scalar tail columns (V = float: P % 4, or unaligned rows)
+// only; the float4 stream is ring_mix_dma_kernel's.
 // Measured on MI355X (tools/membench*.hip, 8192 x 2^20): short-lived tiles win
-// — R = 4 with all R+2 loads issued up front (PF >= R), plain loads and
+// — 4 rows with all 6 loads issued up front (PF >= rows), plain loads and
 // nontemporal stores reach 6.14 TB/s against a 6.26 TB/s flat-copy ceiling,
-// while R = 64 long-lived tiles stay near 5.1-5.4.  The halo rows (2 per
+// while 64-row long-lived tiles stay near 5.1-5.4.  The halo rows (2 per
 // tile) are re-read from L2: vertically adjacent tiles are n_col_tiles
 // blocks apart (a multiple of 8 -> same XCD) and co-resident.
 // ----------------------------------------------------------------------------
-template <typename V, int PF, bool NT_LOAD, bool NT_STORE, class Epi = NoEpi>
+constexpr int kRingTailRows = 4;  // rows per block = rows loaded ahead
+
+template <typename V, class Epi = NoEpi>
 __global__ __launch_bounds__(kThreads) void ring_mix_kernel(
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy,
     int n_rows, int64_t c_off, int64_t ncols_v, int64_t n_col_tiles, int rows_per_block,
@@ -241,16 +269,17 @@ __global__ __launch_bounds__(kThreads) void ring_mix_kernel(
     return reinterpret_cast<const V*>(base + c_off) + c;
   };
 
+  constexpr int PF = kRingTailRows;
   V q[PF + 2];
-  q[0] = ldv<V, NT_LOAD>(row(r0 - 1));
-  q[1] = ldv<V, NT_LOAD>(row(r0));
+  q[0] = *row(r0 - 1);
+  q[1] = *row(r0);
 #pragma unroll
-  for (int k = 0; k < PF; ++k) q[2 + k] = ldv<V, NT_LOAD>(row(min(r0 + 1 + k, r1)));
+  for (int k = 0; k < PF; ++k) q[2 + k] = *row(min(r0 + 1 + k, r1));
 
   for (int i = r0; i < r1; i += PF) {
     V nx[PF];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) nx[k] = ldv<V, NT_LOAD>(row(min(i + PF + 1 + k, r1)));
+    for (int k = 0; k < PF; ++k) nx[k] = *row(min(i + PF + 1 + k, r1));
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
       const int r = i + k;
@@ -258,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void ring_mix_kernel(
         V out = axpy0(wprev[r], q[k], wnext[r], q[k + 2]);
         const int64_t cf = c_off + c * Vec<V>::W;
         out = epi.apply(out, epi.template load<V>(r, cf), r, cf);
-        stv<V, NT_STORE>(reinterpret_cast<V*>(Y + int64_t(r) * ldy + c_off) + c, out);
+        __builtin_nontemporal_store(out, reinterpret_cast<V*>(Y + int64_t(r) * ldy + c_off) + c);
       }
     }
     q[0] = q[PF];
@@ -267,8 +296,6 @@ __global__ __launch_bounds__(kThreads) void ring_mix_kernel(
     for (int k = 0; k < PF; ++k) q[2 + k] = nx[k];
   }
 }
-
-
 
 // The two boundary rows of a sharded ring block in ONE launch (the multi-GPU
 // round, dolhip.parallel.ShardedRing: the interior rows are mixed while the
@@ -301,17 +328,19 @@ __global__ __launch_bounds__(kThreads) void ring_edges_kernel(
 // MI355X (tools/membench7/8.hip, same box): 6.17 TB/s vs 5.91 for the
 // register-staged kernel, = the measured copy ceiling (6.16); nt loads on
 // every row cost 17 % (they evict the halo rows from L2), but nt on the R - 2
-// rows no other tile reads (NTI, default; DOL_RING_NTI=0 turns it off) gains
-// 2.3 %: 10.90-10.93 vs 11.15-11.16 ms at 8192 x 2^20, three A/B pairs on
-// one box (profiles/r01d_ring_nti.txt).  The same split in ring_steps_kernel
-// gained nothing.
+// rows no other tile reads (NTI) gains 2.3 %: 10.90-10.93 vs 11.15-11.16 ms at
+// 8192 x 2^20, three A/B pairs on one box (profiles/r01d_ring_nti.txt).  The
+// same split in ring_steps_kernel gained nothing.
 #define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 // COPY (roofline calibration only): the same loads, cache policies and stores,
 // with the stencil replaced by the tile's own row (Y = X): the memory-system
 // ceiling of exactly this kernel's access pattern.
-template <int R, class Epi = NoEpi, bool NTI = false, bool COPY = false>
+// NTI is always true now; the parameter list stays <R, Epi, NTI, COPY> because
+// bench.py reports the headline's kernel by that name
+// (ring_mix_dma_kernel<4, NoEpi, true, false>).
+template <int R, class Epi, bool NTI, bool COPY>
 __global__ __launch_bounds__(kThreads) void ring_mix_dma_kernel(
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows,
     int64_t ncols_v, int64_t n_col_tiles, const float* __restrict__ halo_prev,
@@ -423,7 +452,7 @@ __global__ __launch_bounds__(kThreads) void ring_steps_kernel(
 // STEPS / R = 45 % halo at R = 22.  The stencil has no diagonal term (circle
 // W: W_ii = 0), so only the two neighbours enter, as in axpy0.
 // ----------------------------------------------------------------------------
-template <int S, int PF, bool INTERIOR, bool NT>
+template <int S, int PF, bool INTERIOR>
 __device__ __forceinline__ void ring_stream_body(const f4* __restrict__ xc, int64_t ldv, float* __restrict__ Y,
                                                  int64_t ldy, int64_t c, int n_rows, int r0, int nT,
                                                  const float* __restrict__ wprev, const float* __restrict__ wnext) {
@@ -439,7 +468,7 @@ __device__ __forceinline__ void ring_stream_body(const f4* __restrict__ xc, int6
   const f4* lp = xc + int64_t(gl) * ldv;
   int left = nsteps;  // input rows not yet issued
   auto next = [&]() {
-    const f4 v = NT ? __builtin_nontemporal_load(lp) : *lp;
+    const f4 v = __builtin_nontemporal_load(lp);
     if (--left > 0) {
       ++gl;
       lp += ldv;
@@ -495,7 +524,7 @@ __device__ __forceinline__ void ring_stream_body(const f4* __restrict__ xc, int6
   }
 }
 
-template <int S, int PF, bool NT>
+template <int S, int PF>
 __global__ __launch_bounds__(kThreads) void ring_stream_kernel(
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows,
     int64_t ncols_v, uint32_t n_col_tiles, const float* __restrict__ wprev,
@@ -512,9 +541,9 @@ __global__ __launch_bounds__(kThreads) void ring_stream_kernel(
   const f4* xc = reinterpret_cast<const f4*>(X) + c;
   const int64_t ldv = ldx / 4;
   if (r0 - 2 * S >= 0 && r0 + nT + S + PF <= n_rows)  // every row and weight index in range
-    ring_stream_body<S, PF, true, NT>(xc, ldv, Y, ldy, c, n_rows, r0, nT, wprev, wnext);
+    ring_stream_body<S, PF, true>(xc, ldv, Y, ldy, c, n_rows, r0, nT, wprev, wnext);
   else
-    ring_stream_body<S, PF, false, NT>(xc, ldv, Y, ldy, c, n_rows, r0, nT, wprev, wnext);
+    ring_stream_body<S, PF, false>(xc, ldv, Y, ldy, c, n_rows, r0, nT, wprev, wnext);
 }
 
 // ----------------------------------------------------------------------------
@@ -542,7 +571,7 @@ __device__ __forceinline__ void vm_wait() {
 using rsrc_t = __amdgpu_buffer_rsrc_t;
 constexpr uint32_t kOOB = 0x80000000u;  // a buffer offset past every range: the access is dropped
 
-template <int S, int D, int PF, bool INTERIOR, int PROBE = 0, bool SYNC = false>
+template <int S, int D, int PF, bool INTERIOR, bool SYNC = false>
 __device__ __forceinline__ void ring_stream_dma_body(const float* __restrict__ X, int64_t ldx, float* __restrict__ Y,
                                                      int64_t ldy, int64_t c, int n_rows, int r0, int nT,
                                                      const float* __restrict__ wprev,
@@ -623,14 +652,12 @@ __device__ __forceinline__ void ring_stream_dma_body(const float* __restrict__ X
       issue(i + D - 1);
       vm_wait<2 * D - 2>();  // L(i) has landed
       f4 nv = *reinterpret_cast<const f4*>(slot0 + u * 256);  // level 0 at index i
-      if constexpr (PROBE == 0) {  // PROBE 1 (diagnostics): a copy in this geometry, no levels
 #pragma unroll
-        for (int t = 1; t <= S; ++t) {
-          f4& hv = (u & 1) ? hB[t - 1] : hA[t - 1];
-          const f4 old = hv;
-          hv = nv;
-          nv = axpy0(wp.v[u + S - t], old, wn.v[u + S - t], nv);
-        }
+      for (int t = 1; t <= S; ++t) {
+        f4& hv = (u & 1) ? hB[t - 1] : hA[t - 1];
+        const f4 old = hv;
+        hv = nv;
+        nv = axpy0(wp.v[u + S - t], old, wn.v[u + S - t], nv);
       }
       store(i, nv);
     }
@@ -638,7 +665,7 @@ __device__ __forceinline__ void ring_stream_dma_body(const float* __restrict__ X
   vm_wait<0>();  // no LDS-DMA may land after the wave's LDS is released
 }
 
-template <int S, int D, int PF, int PROBE = 0, bool SYNC = false>
+template <int S, int D, int PF, bool SYNC = false>
 __global__ __launch_bounds__(kThreads) void ring_stream_dma_kernel(
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows,
     int64_t ncols_v, uint32_t n_col_tiles, const float* __restrict__ wprev,
@@ -664,9 +691,9 @@ __global__ __launch_bounds__(kThreads) void ring_stream_dma_kernel(
   const int nT = min(T, n_rows - r0);
   float* ring = &lds[threadIdx.x >> 6][0][0];
   if (r0 - 2 * S >= 0 && r0 + nT + S + PF <= n_rows)  // every row and weight index in range
-    ring_stream_dma_body<S, D, PF, true, PROBE, SYNC>(X, ldx, Y, ldy, c, n_rows, r0, nT, wprev, wnext, ring, live);
+    ring_stream_dma_body<S, D, PF, true, SYNC>(X, ldx, Y, ldy, c, n_rows, r0, nT, wprev, wnext, ring, live);
   else
-    ring_stream_dma_body<S, D, PF, false, PROBE, SYNC>(X, ldx, Y, ldy, c, n_rows, r0, nT, wprev, wnext, ring, live);
+    ring_stream_dma_body<S, D, PF, false, SYNC>(X, ldx, Y, ldy, c, n_rows, r0, nT, wprev, wnext, ring, live);
 }
 
 // ----------------------------------------------------------------------------
@@ -1451,43 +1478,15 @@ inline ColSplit split_cols(int64_t P, bool vec_ok) {
 
 inline bool row_vec_ok(const void* base, int64_t ld) { return base == nullptr || (aligned16(base) && (ld % 4) == 0); }
 
-template <typename V, int PF, bool NTL, bool NTS, class Epi = NoEpi>
+template <typename V, class Epi = NoEpi>
 void launch_ring(const float* X, int64_t ldx, float* Y, int64_t ldy, int n_rows, int64_t c_off,
                  int64_t ncols_v, int rpb, const float* hp, const float* hn, const float* wp,
                  const float* wn, hipStream_t s, const Epi& epi = Epi{}) {
   const int64_t n_col_tiles = cdiv(ncols_v, kThreads);
   const int64_t n_rg = cdiv(n_rows, rpb);
   const int64_t grid = n_col_tiles * n_rg;
-  hipLaunchKernelGGL((ring_mix_kernel<V, PF, NTL, NTS, Epi>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s,
+  hipLaunchKernelGGL((ring_mix_kernel<V, Epi>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s,
                      X, ldx, Y, ldy, n_rows, c_off, ncols_v, n_col_tiles, rpb, hp, hn, wp, wn, epi);
-}
-
-template <typename V>
-void launch_ring_variant(int pf, int nt, const float* X, int64_t ldx, float* Y, int64_t ldy,
-                         int n_rows, int64_t c_off, int64_t ncols_v, int rpb, const float* hp,
-                         const float* hn, const float* wp, const float* wn, hipStream_t s) {
-  // nt bit0 = nontemporal loads, bit1 = nontemporal stores
-#define DOL_RING_CASE(PFV, NTL, NTS)                                                         \
-  if (pf == PFV && nt == (NTL + 2 * NTS)) {                                                \
-    launch_ring<V, PFV, NTL, NTS>(X, ldx, Y, ldy, n_rows, c_off, ncols_v, rpb, hp, hn, wp, wn, s); \
-    return;                                                                                \
-  }
-  DOL_RING_CASE(2, 0, 1)
-  DOL_RING_CASE(4, 0, 1)
-  DOL_RING_CASE(8, 0, 1)
-  DOL_RING_CASE(4, 0, 0)
-  DOL_RING_CASE(4, 1, 1)
-  DOL_RING_CASE(8, 1, 1)
-  DOL_RING_CASE(4, 1, 0)
-#undef DOL_RING_CASE
-  launch_ring<V, 4, false, true>(X, ldx, Y, ldy, n_rows, c_off, ncols_v, rpb, hp, hn, wp, wn, s);
-}
-
-int ring_rows_per_block(int n_rows, int64_t n_col_tiles, int pf) {
-  int r = env_int("DOL_RING_ROWS", 0);
-  if (r > 0) return r;
-  (void)n_col_tiles;
-  return pf < 4 ? pf : 4;  // see the ring kernel comment: 4 rows per tile, all loads up front
 }
 
 template <typename V, int RPB, class Epi = NoEpi>
@@ -1554,30 +1553,22 @@ int mix_csr_impl(const char* nm, const float* X, int64_t ldx, int32_t x_rows, fl
   const ColSplit cs = split_cols(P, vec_ok);
   constexpr int RPB = 16;
   constexpr int XW = 32, XPASSES = 2;  // XCD-pinned tiles: 512 B of a row, 16 rows per block
-  // 0 = 4 KiB tiles, 1 = XCD-pinned (DOL_CSR_MODE; default: XCD-pinned from 512 rows)
+  // 0 = 4 KiB tiles, 1 = XCD-pinned (DOL_CSR_MODE; default: XCD-pinned from 512 rows).
+  // The switch stays: both kernels it selects are live under the automatic rule.
   const int mode = env_int("DOL_CSR_MODE", -1);
   if (mul_sat(cdiv(cs.n4, kThreads), cdiv(n_rows, RPB)) > kMaxBlocks)
     return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
   int64_t done4 = 0;
   const bool use_xcd = cs.n4 >= XW && (mode == 1 || (mode < 0 && n_rows >= 512));
   if (use_xcd) {
-    const int passes = env_int("DOL_CSR_PASSES", XPASSES);
-    auto go = [&](auto pc) {
-      constexpr int PS = decltype(pc)::value;
-      const int64_t nt = cs.n4 / XW;
-      const int64_t nrb = cdiv(n_rows, (kThreads / XW) * PS);
-      const int64_t grid = cdiv(nt, 8) * 8 * nrb;
-      if (grid > kMaxBlocks * 8) return false;
-      hipLaunchKernelGGL((csr_xcd_kernel<XW, PS, Epi>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s, X,
-                         ldx, Y, ldy, n_rows, static_cast<uint32_t>(nrb), static_cast<uint32_t>(nt), rowptr, col,
-                         val, epi);
-      done4 = nt * XW;
-      return true;
-    };
-    using std::integral_constant;
-    const bool ok = passes == 1 ? go(integral_constant<int, 1>{})
-                    : passes == 4 ? go(integral_constant<int, 4>{}) : go(integral_constant<int, XPASSES>{});
-    if (!ok) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+    const int64_t nt = cs.n4 / XW;
+    const int64_t nrb = cdiv(n_rows, (kThreads / XW) * XPASSES);
+    const int64_t grid = cdiv(nt, 8) * 8 * nrb;
+    if (grid > kMaxBlocks * 8) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+    hipLaunchKernelGGL((csr_xcd_kernel<XW, XPASSES, Epi>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s, X,
+                       ldx, Y, ldy, n_rows, static_cast<uint32_t>(nrb), static_cast<uint32_t>(nt), rowptr, col, val,
+                       epi);
+    done4 = nt * XW;
   }
   if (cs.n4 > done4)  // column offset through c_off so the epilogue sees absolute columns
     launch_csr<f4, RPB, Epi>(X, ldx, Y, ldy, n_rows, done4 * 4, cs.n4 - done4, rowptr, col, val, s, epi);
@@ -1590,7 +1581,6 @@ template <class Epi>
 int mix_ring_impl(const char* nm, const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n_rows, int64_t P,
                   const float* halo_prev, const float* halo_next, const float* w_prev, const float* w_next,
                   const Epi& epi, bool epi_vec_ok, hipStream_t s) {
-  constexpr bool kPlain = std::is_same<Epi, NoEpi>::value;
   if (n_rows < 0 || P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
   if (n_rows == 0 || P == 0) { g_err[0] = '\0'; return DOL_OK; }
   if (!X || !Y || !w_prev || !w_next) return fail(DOL_EINVAL, "%s: null pointer", nm);
@@ -1606,32 +1596,17 @@ int mix_ring_impl(const char* nm, const float* X, int64_t ldx, float* Y, int64_t
                       epi_vec_ok;
   const ColSplit cs = split_cols(P, vec_ok);
   if (cs.n4 > 0) {
+    constexpr int R = 4;
     const int64_t nct = cdiv(cs.n4, kThreads);
-    bool dma = true;
-    if constexpr (kPlain) dma = env_int("DOL_RING_DMA", 1) != 0;
-    if (dma) {
-      constexpr int R = 4;
-      if (mul_sat(nct, cdiv(n_rows, R)) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
-      if (env_int("DOL_RING_NTI", 1))
-        hipLaunchKernelGGL((ring_mix_dma_kernel<R, Epi, true>), dim3(static_cast<unsigned>(nct * cdiv(n_rows, R))),
-                           dim3(kThreads), 0, s, X, ldx, Y, ldy, n_rows, cs.n4, nct, halo_prev, halo_next, w_prev, w_next, epi);
-      else
-      hipLaunchKernelGGL((ring_mix_dma_kernel<R, Epi>), dim3(static_cast<unsigned>(nct * cdiv(n_rows, R))), dim3(kThreads),
-                         0, s, X, ldx, Y, ldy, n_rows, cs.n4, nct, halo_prev, halo_next, w_prev, w_next, epi);
-    } else if constexpr (kPlain) {
-      const int pf = env_int("DOL_RING_PF", 4);
-      const int nt = env_int("DOL_RING_NT", 2);
-      const int rpb = ring_rows_per_block(n_rows, nct, pf);
-      if (mul_sat(nct, cdiv(n_rows, rpb)) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
-      launch_ring_variant<f4>(pf, nt, X, ldx, Y, ldy, n_rows, 0, cs.n4, rpb, halo_prev, halo_next, w_prev, w_next, s);
-    }
+    if (mul_sat(nct, cdiv(n_rows, R)) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+    hipLaunchKernelGGL((ring_mix_dma_kernel<R, Epi, true, false>), dim3(static_cast<unsigned>(nct * cdiv(n_rows, R))),
+                       dim3(kThreads), 0, s, X, ldx, Y, ldy, n_rows, cs.n4, nct, halo_prev, halo_next, w_prev, w_next, epi);
   }
   if (cs.tail > 0) {
-    const int rpb = ring_rows_per_block(n_rows, cdiv(cs.tail, kThreads), 4);
-    if (mul_sat(cdiv(cs.tail, kThreads), cdiv(n_rows, rpb)) > kMaxBlocks)
+    if (mul_sat(cdiv(cs.tail, kThreads), cdiv(n_rows, kRingTailRows)) > kMaxBlocks)
       return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
-    launch_ring<float, 4, false, true, Epi>(X, ldx, Y, ldy, n_rows, cs.n4 * 4, cs.tail, rpb, halo_prev, halo_next,
-                                            w_prev, w_next, s, epi);
+    launch_ring<float, Epi>(X, ldx, Y, ldy, n_rows, cs.n4 * 4, cs.tail, kRingTailRows, halo_prev, halo_next, w_prev,
+                            w_next, s, epi);
   }
   return check_launch(nm);
 }
@@ -1949,7 +1924,7 @@ int dol_mix_dense_f32(const float* W, int64_t ldw, const float* X, int64_t ldx, 
 }
 
 // kernel of dol_mix_ring_steps_f32 chosen by dol_ring_steps_set_variant (0:
-// DOL_RING_STREAM); atomic, so a setter on one thread never tears a launch's
+// the register tiles); atomic, so a setter on one thread never tears a launch's
 // read on another (dol_mix_ring_steps_ex_f32 takes the variant per call)
 static std::atomic<int> g_ring_steps_variant{0};
 
@@ -1982,8 +1957,11 @@ int dol_mix_ring_steps_ex_f32(const float* X, int64_t ldx, float* Y, int64_t ldy
   if (steps == 0) return fail(DOL_EINVAL, "dol_mix_ring_steps_f32: steps must be >= 1");
   const bool vec = row_vec_ok(X, ldx) && row_vec_ok(Y, ldy) && P % 4 == 0;
   if (!vec || steps > 8) return fail(DOL_EINVAL, "dol_mix_ring_steps_f32: needs 16-B aligned rows, P %% 4 == 0 and steps <= 8 (compose launches otherwise)");
-  // The register-tile ring_steps_kernel unless DOL_RING_STREAM=1
-  // (ring_stream_kernel: 1024-row tiles, 8 rows in flight, nontemporal loads).
+  // Five kernels give the same bits; the variant picks one: 1 ring_steps_kernel
+  // (register tiles), 2 ring_stream_kernel (1024-row tiles, 8 rows in flight,
+  // nontemporal loads), 3 / 4 / 5 ring_stream_dma_kernel (plain / block-
+  // synchronised / column-tile-fastest sweep of 64-row tiles).  Variant 0 is
+  // the process setting (dol_ring_steps_set_variant), else the register tiles.
   // eps = 5 at 8192 x 2^20, alternating on one box (profiles/r03_eps_stream.txt):
   // box A stream 12.38 / 12.39 vs tiles 12.61 / 12.62 ms; box C stream-NT 11.60 /
   // 12.00 / 11.76 vs tiles 11.90 / 11.92 / 11.80; box E stream-NT 12.95-13.19 vs
@@ -1991,87 +1969,38 @@ int dol_mix_ring_steps_ex_f32(const float* X, int64_t ldx, float* Y, int64_t ldy
   // on another with the same ring round (10.92 ms): no consistent winner, so the
   // r02 default stays.  Clock 1 % below the ring kernel's for both (2424 / 2408
   // vs 2439 MHz, GRBM_GUI_ACTIVE per XCD over the kernel's time).
-  // Which of the two wins follows where the bank's pages landed, as for the
+  // Which variant wins follows where the bank's pages landed, as for the
   // parameter-major mix (profiles/r03_pm_stage_order.txt): ops.tune_ring_steps_variant
-  // times both on the buffers in use and keeps the faster (dol_ring_steps_set_variant).
-  static const int stream_env = [] { const char* e = getenv("DOL_RING_STREAM"); return e ? atoi(e) : 0; }();
+  // times them on the buffers in use and keeps the fastest (dol_ring_steps_set_variant).
   const int v = variant != 0 ? variant : g_ring_steps_variant.load(std::memory_order_relaxed);
-  // stream: 0 register tiles, 1 register stream, 3 / 4 / 5 LDS-DMA stream
-  // (plain / block-synchronised / column-tile-fastest sweep of 64-row tiles)
-  const int stream = v == 0 ? stream_env : (v == 2 ? 1 : v >= 3 ? v : 0);
-  static const int stream_t = [] { const char* e = getenv("DOL_RING_STREAM_T"); return e ? atoi(e) : 1024; }();
-  static const int stream_pf = [] { const char* e = getenv("DOL_RING_STREAM_PF"); return e ? atoi(e) : 8; }();
-  static const int stream_nt = [] { const char* e = getenv("DOL_RING_STREAM_NT"); return e ? atoi(e) : 1; }();
-  auto go_stream_pf = [&](auto steps_c, int T, auto pf_c) {
-    constexpr int S = decltype(steps_c)::value, PF = decltype(pf_c)::value;
-    const int64_t nv = P / 4;
-    const uint32_t nct = static_cast<uint32_t>(cdiv(nv, kThreads));
-    const int64_t nrt = cdiv(n_rows, T);
-    const int64_t grid = cdiv(nct, 8) * 8 * nrt;
-    if (grid > kMaxBlocks) return fail(DOL_EINVAL, "dol_mix_ring_steps_f32: too large");
-    // DOL_RING_STREAM_LDS (diagnostics): bytes of unused LDS per block, to cap
-    // the blocks per CU (the kernel itself uses none)
-    static const int pad_lds = [] { const char* e = getenv("DOL_RING_STREAM_LDS"); return e ? atoi(e) : 0; }();
-    auto go_k = [&](auto kern) {
-      if (pad_lds > 65536)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pad_lds);
-      hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreads), pad_lds, s, X, ldx, Y, ldy, n_rows, nv,
-                         nct, w_prev, w_next, static_cast<uint32_t>(nrt), T);
-    };
-    if (stream_nt) go_k(ring_stream_kernel<S, PF, true>);
-    else go_k(ring_stream_kernel<S, PF, false>);
-    return check_launch("dol_mix_ring_steps_f32");
-  };
-  // variant 3: ring_stream_dma_kernel, D-row LDS-DMA ring per wave (DOL_RING_DMA_D 8 / 16)
-  static const int dma_d = [] { const char* e = getenv("DOL_RING_DMA_D"); return e ? atoi(e) : 8; }();
-  // DOL_RING_DMA_SYNC=1: one raw barrier per 8 steps keeps a block's waves on the same rows
-  static const int dma_sync = [] { const char* e = getenv("DOL_RING_DMA_SYNC"); return e ? atoi(e) : 0; }();
-  // DOL_RING_DMA_ORDER: 0 = XCD-aware row-tile order, 1 = column tile fastest (sweep)
-  static const int dma_order = [] { const char* e = getenv("DOL_RING_DMA_ORDER"); return e ? atoi(e) : 0; }();
-  auto go_stream_dma = [&](auto steps_c, int T) {
+  const bool stream = v >= 2;
+  auto go_stream = [&](auto steps_c) {
     constexpr int S = decltype(steps_c)::value;
-    const bool sync = stream == 4 || dma_sync;
-    const int order = stream == 5 ? 1 : dma_order;
-    if (stream == 5) T = 64;
+    const int T = v == 5 ? 64 : 1024;  // tile rows
     const int64_t nv = P / 4;
     const uint32_t nct = static_cast<uint32_t>(cdiv(nv, kThreads));
     const int64_t nrt = cdiv(n_rows, T);
     const int64_t grid = cdiv(nct, 8) * 8 * nrt;
     if (grid > kMaxBlocks) return fail(DOL_EINVAL, "dol_mix_ring_steps_f32: too large");
-    // DOL_RING_DMA_PROBE=1 (diagnostics, wrong results): the same kernel as a copy
-    static const int dma_probe = [] { const char* e = getenv("DOL_RING_DMA_PROBE"); return e ? atoi(e) : 0; }();
-    if constexpr (S == 5) {
-      if (dma_probe == 1) {
-        hipLaunchKernelGGL((ring_stream_dma_kernel<S, 8, 8, 1>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s,
-                           X, ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next, static_cast<uint32_t>(nrt), T, order);
-        return check_launch("dol_mix_ring_steps_f32");
-      }
-    }
-    if (sync)
-      hipLaunchKernelGGL((ring_stream_dma_kernel<S, 8, 8, 0, true>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s,
-                         X, ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next, static_cast<uint32_t>(nrt), T, order);
-    else if (dma_d == 16)
-      hipLaunchKernelGGL((ring_stream_dma_kernel<S, 16, 8>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s, X,
-                         ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next, static_cast<uint32_t>(nrt), T, order);
-    else
-      hipLaunchKernelGGL((ring_stream_dma_kernel<S, 8, 8>), dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s, X,
-                         ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next, static_cast<uint32_t>(nrt), T, order);
+    const dim3 g(static_cast<unsigned>(grid)), b(kThreads);
+    const uint32_t nrt32 = static_cast<uint32_t>(nrt);
+    const int order = v == 5 ? 1 : 0;  // 0 = XCD-aware row-tile order, 1 = column tile fastest (sweep)
+    if (v == 2)
+      hipLaunchKernelGGL((ring_stream_kernel<S, 8>), g, b, 0, s, X, ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next, nrt32, T);
+    else if (v == 4)  // one raw barrier per 8 steps keeps a block's waves on the same rows
+      hipLaunchKernelGGL((ring_stream_dma_kernel<S, 8, 8, true>), g, b, 0, s, X, ldx, Y, ldy, n_rows, nv, nct, w_prev,
+                         w_next, nrt32, T, order);
+    else  // 8-row LDS-DMA ring per wave
+      hipLaunchKernelGGL((ring_stream_dma_kernel<S, 8, 8>), g, b, 0, s, X, ldx, Y, ldy, n_rows, nv, nct, w_prev, w_next,
+                         nrt32, T, order);
     return check_launch("dol_mix_ring_steps_f32");
-  };
-  auto go_stream = [&](auto steps_c, int T) {
-    if (stream >= 3) return go_stream_dma(steps_c, T);
-    if (stream_pf == 16) return go_stream_pf(steps_c, T, std::integral_constant<int, 16>{});
-    if (stream_pf == 4) return go_stream_pf(steps_c, T, std::integral_constant<int, 4>{});
-    return go_stream_pf(steps_c, T, std::integral_constant<int, 8>{});
   };
 
   auto go_v = [&](auto steps_c, auto r_c, auto v_c) {
     constexpr int S = decltype(steps_c)::value, R = decltype(r_c)::value;
-    // the stream kernels wrap at most once (PF <= 16); the LDS-DMA one's buffer
-    // stores address a row in 32 bits
-    if (stream && n_rows >= 2 * S + 16 + 1 && (stream < 3 || ldy * 4 < (int64_t(1) << 31))) {
-      return go_stream(steps_c, stream_t >= 64 ? stream_t : 1024);
-    }
+    // the stream kernels wrap at most once, so smaller rings take the register
+    // tiles; the LDS-DMA one's buffer stores address a row in 32 bits
+    if (stream && n_rows >= 2 * S + 16 + 1 && (v < 3 || ldy * 4 < (int64_t(1) << 31))) return go_stream(steps_c);
     using V = typename decltype(v_c)::type;
     const int64_t nv = P / Vec<V>::W;
     const uint32_t nct = static_cast<uint32_t>(cdiv(nv, kThreads));
@@ -2309,15 +2238,13 @@ int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, f
                       row_vec_ok(theta, 0) && row_vec_ok(theta_out, 0) && (!mom || row_vec_ok(buf, ldb));
   const ColSplit cs = split_cols(P, vec_ok);
   // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
-  // one workgroup per CU at 2^20 columns) unless DOL_ADMM_ROUND_THREADS=256.
-  // Narrower blocks (fewer than 1024 lanes per CU) take 256-lane strips: the
-  // strips are the only parallelism (the sum over agents is sequential per
-  // column).  At 8192 x 2^17 (a column-sharded rank's block at 8 ranks):
-  // 18.6 ms with 1024-lane strips, 7.4 with 256, 7.65 with one-wave strips
-  // and 8 agents in flight -- and 5.15 for the two-kernel round (row-major
-  // client round + ordered sum), which SeparableADMM(shard="columns") takes
-  // there (profiles/r06c_admm_narrow_ab.jsonl).
-  static const int threads_env = env_int("DOL_ADMM_ROUND_THREADS", 0);
+  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
+  // lanes per CU) take 256-lane strips: the strips are the only parallelism
+  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
+  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
+  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
+  // for the two-kernel round (row-major client round + ordered sum), which
+  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
   static const int n_cu = [] {
     int dev = 0, cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -2325,8 +2252,7 @@ int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, f
     return cu > 0 ? cu : 256;
   }();
   const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
-  const int nt = threads_env == 256 || threads_env == 64 || threads_env == 1024 ? threads_env
-                 : (lanes >= int64_t(1024) * n_cu ? 1024 : 256);
+  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
   const bool wide = nt == 1024;
   const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
   const int64_t nb = nb4 + nbt;
@@ -2335,8 +2261,7 @@ int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, f
   auto go = [&](auto vt, auto mc, auto rc, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
     using V = decltype(vt);
     constexpr bool M = decltype(mc)::value, R = decltype(rc)::value;
-    auto k = wide ? admm_ls_round_mean_kernel<V, M, R, 1024>
-                  : nt == 256 ? admm_ls_round_mean_kernel<V, M, R, 256> : admm_ls_round_mean_kernel<V, M, R, 64, 8>;
+    auto k = wide ? admm_ls_round_mean_kernel<V, M, R, 1024> : admm_ls_round_mean_kernel<V, M, R, 256>;
     hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, alpha,
                        lda, target, ldt, theta, agents, first, m, c_off, ncols, rho, -lr, momentum, local_steps,
                        theta_out, scale, do_div, partial, part_off, nb);

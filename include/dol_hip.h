@@ -102,7 +102,7 @@ int dol_pm_set_stage_order(int32_t nseg);
  * streaming with the rows arriving by LDS-DMA (ring_stream_dma_kernel: plain,
  * block-synchronised once per 8 rows, 64-row tiles in column-tile-fastest
  * order); the streaming kernels need n_rows >= 2 * steps + 17 (else tiles).
- * 0 = the default (DOL_RING_STREAM, else tiles).  Same bits for every
+ * 0 = the default (register tiles).  Same bits for every
  * variant.  Returns the previous setting, or DOL_EINVAL outside [0, 5].
  * No reference counterpart (a launch choice of this implementation).  Atomic,
  * like dol_pm_set_stage_order; dol_mix_ring_steps_ex_f32 takes it per call.

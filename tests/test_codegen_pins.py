@@ -1,7 +1,7 @@
 """Pins on the emitted gfx950 code of the counted-wait LDS-DMA kernels (CPU
 tier: reads the code object hipcc built, runs nothing).
 
-ring_stream_dma_kernel<S, D, PF, ...> (FedLCon's eps pass, variants 3-5 of
+ring_stream_dma_kernel<S, D, PF, SYNC> (FedLCon's eps pass, variants 3-5 of
 dol_mix_ring_steps_ex_f32) is bit-exact only if every `s_waitcnt vmcnt(N)` it
 executes retires exactly the LDS-DMA row about to be read.  Its accounting
  assumes one vector-memory counter that counts loads AND
@@ -68,9 +68,9 @@ def test_ring_stream_dma_waits_are_counted(code_object):
     ks = _kernels(code_object, "ring_stream_dma_kernel")
     assert ks, "no ring_stream_dma_kernel instantiations in the code object"
     for k in ks:
-        m = re.search(r"ring_stream_dma_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", k)
+        m = re.search(r"ring_stream_dma_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", k)
         assert m, k
-        S, D, PF, probe, sync = map(int, m.groups())
+        S, D, PF, sync = map(int, m.groups())
         asm = _disasm(code_object, k)
         waits = [int(v) for v in re.findall(r"s_waitcnt vmcnt\((\d+)\)", asm)]
         assert waits, f"{k}: no vmcnt waits"

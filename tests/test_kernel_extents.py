@@ -8,11 +8,12 @@ mapped to exactly rows * ld * 4 bytes (rounded to the 2 MiB granularity) it
 faults, so every kernel must stay inside its rows.
 
 Restated (csrc/dol_hip.hip, function and index expressions named per case):
-  * ring_mix_dma_kernel<4, DgdEpi, NTI> -- the ring DGD round's float4 body
+  * ring_mix_dma_kernel<4, DgdEpi, true, false> -- the ring DGD round's float4 body
     (mix_ring_impl: grid nct * cdiv(n, 4)); R + 2 row loads per block at
     min(r0 - 1 + k, r1) through row() (halo pointers below 0 / from n), the
     epilogue's target / momentum loads at min(r0 + k, r1 - 1), stores r < r1;
-  * ring_mix_kernel<float, 4> -- the same round's P % 4 tail columns;
+  * ring_mix_kernel<float, DgdEpi> -- the same round's P % 4 tail columns
+    (4 rows per block);
   * ring_edges_kernel -- rows 0 and n - 1 of a sharded block;
   * csr_xcd_kernel<32, 2, DgdEpi> -- the random-regular DGD round (mix_csr_impl
     from 512 rows), rows clamped to n - 1 on the degree-4 fast path;
@@ -84,7 +85,7 @@ def _add_rows(e, r, n, ld, c_lo, c_hi, wrap_halos):
 
 
 def ring_dma_extents(n, P, ld, mode, wrap_halos=True, R=4):
-    """mix_ring_impl -> ring_mix_dma_kernel<R, DgdEpi<*, mode>, NTI> + the float tail."""
+    """mix_ring_impl -> ring_mix_dma_kernel<R, DgdEpi<*, mode>, true, false> + the float tail."""
     e = Ext()
     n4, tail = split_cols(P)
     if n4:
@@ -108,7 +109,7 @@ def ring_dma_extents(n, P, ld, mode, wrap_halos=True, R=4):
                 e.add("Y", rs * ld + 4 * c_lo[st], rs * ld + 4 * c_hi[st] + 3)
                 if mode:
                     e.add("M", rs * ld + 4 * c_lo[st], rs * ld + 4 * c_hi[st] + 3)
-    if tail:  # ring_mix_kernel<float, PF 4> over columns [4 n4, P), rows_per_block 4
+    if tail:  # ring_mix_kernel<float, DgdEpi> (PF = 4) over columns [4 n4, P), rows_per_block 4
         c_off, rpb, PF = 4 * n4, 4, 4
         for r0 in range(0, n, rpb):
             r1 = min(r0 + rpb, n)

@@ -3,8 +3,6 @@ vectors.  Mixing, dual update, ordered mean and the fused local step are
 bit-exact (fp32, same rounding sequence as the reference's torch CPU path);
 the only tolerance is on the fp64 residual norm (a diagnostic whose
 reduction order differs): rtol 1e-12."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -638,8 +636,8 @@ def ring_variant(request):
 
 
 @pytest.mark.parametrize("steps", [1, 2, 3, 4, 5, 6, 7, 8])
-@pytest.mark.parametrize("n,P", [(3, 8), (17, 4100), (64, 1024 * 5), (200, 1024), (1001, 2048), (1600, 4100),
-                                 (2048, 1024)])
+@pytest.mark.parametrize("n,P", [(3, 8), (17, 4100), (40, 256), (64, 1024 * 5), (200, 1024), (1001, 2048),
+                                 (1600, 4100), (2048, 1024)])
 def test_ring_steps_bit_identical_to_single_rounds(steps, n, P, ring_variant, gpu):
     """Both kernels of the fused pass: the register tiles and ring_stream_kernel
     (when n >= 2 steps + 17; 1024-row tiles: 1600 / 2048 rows have interior
@@ -908,39 +906,3 @@ def test_ring_edges_match_oracle(n, P, extra, gpu):
     gm = Md[:, :P].cpu().numpy()
     assert bits_equal(gm[edges], wm[edges])
     assert bits_equal(gm[1:n - 1], M[1:n - 1]), "interior momentum touched"
-
-
-_STREAM_CHILD = r"""
-import sys, numpy as np, torch
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
-import oracle
-from dolhip import ops
-dev = torch.device("cuda:0")
-for steps, n, P in ((5, 4096, 1028), (2, 1600, 4100), (8, 2048, 1024), (3, 40, 256)):
-    rng = np.random.default_rng(steps * 7 + n)
-    X = rng.standard_normal((n, P)).astype(np.float32)
-    wp, wn = rng.random(n).astype(np.float32), rng.random(n).astype(np.float32)
-    want = X
-    for _ in range(steps):
-        want = oracle.mix_ring(want, wp, wn)
-    Y = torch.empty(n, P, device=dev)
-    ops.mix_ring_steps(torch.from_numpy(X).to(dev), Y, torch.from_numpy(wp).to(dev), torch.from_numpy(wn).to(dev), steps)
-    torch.cuda.synchronize()
-    assert oracle.bits_equal(Y.cpu().numpy(), want), (steps, n, P)
-print("ok")
-"""
-
-
-@pytest.mark.parametrize("env", [{"DOL_RING_STREAM": "1"}, {"DOL_RING_STREAM": "1", "DOL_RING_STREAM_NT": "0",
-                                                               "DOL_RING_STREAM_T": "2048"}])
-def test_ring_stream_kernel_opt_in_bit_identical(env, gpu):
-    """The opt-in streaming eps pass (DOL_RING_STREAM=1, read once per process:
-    run in a child) is bit-identical to single rounds: interior and edge tiles,
-    short last tiles, and the small-ring fallback to the register tiles."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", _STREAM_CHILD, root,
-                        os.path.join(root, "distributed-optimization-and-learning_amd")],
-                       env=dict(os.environ, **env), capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]

@@ -2,7 +2,7 @@
 2^20, 10 local steps, momentum, frac 1): the one-pass round + mean
 (dol_admm_ls_round_mean_f32) and the two-kernel round (dol_admm_ls_round_f32 +
 the ordered mean), each kernel by HIP events on the launch stream.  One JSON
-line; run once per DOL_ADMM_ROUND_THREADS setting (read once per process).
+line.
 
   python tools/admm_round_ab.py [--agents N] [--params P] [--rounds R]
 """
@@ -69,7 +69,7 @@ def main():
     mean = [x.elapsed_time(y) for x, y in mean_ev]
     row_bytes = N * P * 4
     ms_f = min(fused)
-    print(json.dumps({"agents": N, "params": P, "round_threads": os.environ.get("DOL_ADMM_ROUND_THREADS", "1024"),
+    print(json.dumps({"agents": N, "params": P,
                       "round_mean_ms": fused, "round_mean_GBps_best": (6 * row_bytes + 8 * P) / ms_f / 1e6,
                       "client_round_ms": rnd, "client_round_GBps_best": 6 * row_bytes / min(rnd) / 1e6,
                       "ordered_mean_ms": mean, "two_kernel_best_ms": min(rnd) + min(mean)}), flush=True)

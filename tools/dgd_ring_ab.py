@@ -1,6 +1,6 @@
 """Config 3's fused ring DGD round (SeparableDGD: least squares + momentum
 0.9, 1024 agents x 2^20, dol_dgd_ring_f32 = ring_mix_dma_kernel<DgdEpi>):
-ms per round by HIP events, for the PMC passes of tools/gpu_r06f.sh.
+ms per round by HIP events, for PMC passes (its driver script was removed; last at 1a824fc).
   python tools/dgd_ring_ab.py [--reps 10] [--objective least_squares]
 """
 import argparse

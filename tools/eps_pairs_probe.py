@@ -71,7 +71,7 @@ def main():
                 print(json.dumps({"va_align": align, "pair": pair, "eps_ms": {v: round(t, 3) for v, t in eps[pair].items()},
                                   "ring_ms": round(ring[pair], 3), "pm_ms": round(pm.get(pair, 0.0), 3)}),
                       file=sys.stderr, flush=True)
-        print(json.dumps({"variants": a.variants, "band_r": os.environ.get("DOL_RING_BAND_R"),
+        print(json.dumps({"variants": a.variants,
                           "alloc": "torch" if a.torch else "mapped", "ld": ld, "va_align": align,
                           "bases": {k: m.data_ptr() for k, m in mats.items()}, "eps_ms": eps, "ring_ms": ring}),
               flush=True)

@@ -41,8 +41,7 @@ def main():
 
     ring = timed(lambda: ops.mix_ring(X, Y, wp, wn))
     ms = timed(lambda: ops.mix_ring_steps(X, Y, wp, wn, a.eps))
-    print(json.dumps({"eps": a.eps, "fz": os.environ.get("DOL_RING_STEPS_FZ", "1"), "ring_ms": ring,
-                      "pass_ms": ms, "pass_TBps": 2 * N * P * 4 / ms / 1e9}), flush=True)
+    print(json.dumps({"eps": a.eps, "ring_ms": ring, "pass_ms": ms, "pass_TBps": 2 * N * P * 4 / ms / 1e9}), flush=True)
 
 
 if __name__ == "__main__":

@@ -67,7 +67,6 @@ def main():
             res.setdefault(f"{v}~", []).append(timed(alt))
     best = {k: min(v) for k, v in res.items()}
     print(json.dumps({"eps": a.eps, "agents": N, "params": P, "ld": X.stride(0),
-                      "dma_d": os.environ.get("DOL_RING_DMA_D", "8"),
                       "ms": res, "best_ms": best,
                       "best_TBps": {k: 2 * N * P * 4 / v / 1e9 for k, v in best.items()}}), flush=True)
 

@@ -1,4 +1,4 @@
-"""Summarise tools/gpu_r06j.sh: per pass, per ordered pair, the eps pass's and
+"""Summarise the r06j pair-counter passes (driver script removed; last at 1a824fc): per pass, per ordered pair, the eps pass's and
 the ring round's median duration (kernel trace) and median counters (PMC),
 for the eps_pair_counters.py run of that pass.  One JSON line per (pass, pair)."""
 import csv
