@@ -29,7 +29,7 @@
 //     2.1 ms vs 0.24 ms of staging at 1024 x 101,770);
 //   * each wave walks its 8 rows' chunk segments as one contiguous run of
 //     entry PAIRS (pads included: a pad reads a zero piece and adds +0), the
-//     next two pairs always in flight behind the current pairs' gathers: per
+//     next pairs always in flight behind the current pair's gathers: per
 //     entry one conflict-free ds_read_b128 gather (1 KiB: the wave reads one
 //     agent's whole piece) + 4 separately rounded mul / add, per pair one
 //     uniform ds_read_b128 of the index.  Chunks are visited in ascending agent
@@ -41,11 +41,40 @@
 // add).  The row groups of one slab sit on one XCD at the same time
 // (blockIdx % 8 = XCD), so the slab's chunks come from HBM once and from that
 // XCD's L2 for the others.
+//
+// Tried and retired (each was a launch variant behind an environment switch or
+// dol_slab_set_variant; the code last existed in commit 2d96633; times at
+// 1024 x 101,770):
+//  * variant 1 (r03), a loop per (row, chunk) segment: pairs two at a time with
+//    the next two pairs' index read behind the gathers, the next row's first
+//    two pairs prefetched, tail cases for a segment's last 1-3 pairs (~30
+//    instructions of loop entry, tails and prefetch per 6.4-entry segment):
+//    0.901-0.907 ms against the asm stream's 0.856-0.862
+//    (profiles/r06p_slab_variant3_ab.jsonl).  dol_slab_set_variant rejects 1;
+//    2 and 3 keep their numbers.
+//  * DOL_SLAB_PROBE 1-7, kernels with wrong results on purpose that drop the
+//    gathers, the X staging, the chunk barrier, the index reads, the
+//    multiplies or the tails to bound each part (profiles/r02_slab_probe.txt).
+//  * DOL_SLAB_ALIGN=4, segments padded to pairs of pairs so the row loop's
+//    tail was at most one step (went with the row loop; the packing pads to
+//    pairs).
+//  * DOL_SLAB_PERSIST=0, one workgroup per item instead of the persistent
+//    grid; DOL_SLAB_KERNEL, the process default variant from the environment
+//    (it is 3).
+//  * Earlier forms of the row loop (profiles/r02_slab_probe.txt): index by
+//    v_readlane from a lane-distributed group index (1.17 ms vs 1.12 with
+//    ds_read2_b64 pairs; one ds_read_b128 per pair then halved the LDS
+//    cycles); windows of 4 / 8 entries across row boundaries with the
+//    accumulator chosen by a uniform switch on a row tag (5.4 ms); row pairs
+//    in lockstep, clamped reads, branch-skipped arithmetic (1.73 ms); steps of
+//    up to 4 entries of one row with the next step's index read across rows
+//    (1.35 ms); index by scalar loads (2.1 ms); chunk headers by s_load
+//    instead of vector loads issued with the chunk's DMA (1.135-1.147 vs
+//    1.105-1.12 ms).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/dol_hip.h"
 #include "dol_common.h"
@@ -71,7 +100,7 @@ constexpr int kZeroRel = kXBytes;
 constexpr int kIdxBytes = 15 * 1024;          // index block capacity per chunk (1920 entries)
 constexpr int kIdxBase = 2 * kStage;
 constexpr int kLds = 2 * kStage + 2 * kIdxBytes;
-// index bytes a stream variant reads past a wave's run (variant 2: two pairs;
+// index bytes the stream reads past a wave's run (variant 2: two pairs;
 // variant 3: DOL_SLAB_STREAM_AHEAD pairs)
 constexpr int kAhead = 16 * (DOL_SLAB_STREAM_AHEAD > 2 ? DOL_SLAB_STREAM_AHEAD : 2);
 constexpr int kRW = 8;                        // rows per wave
@@ -111,27 +140,11 @@ __device__ __forceinline__ f4 fmac(f4 acc, float w, f4 x) { return acc + x * w; 
 // LDS byte address of entry word `o`'s piece for this lane (stage base + lane * 16 in `lb`)
 __device__ __forceinline__ uint32_t piece_addr(uint32_t o, uint32_t lb) { return o + lb; }
 
-// PROBE (diagnostics, DOL_SLAB_PROBE; results meaningless except 0): 1 = staging
-// only (no gathers), 2 = no X staging (index blocks and gathers only), 3 = no
-// workgroup barrier per chunk (waves drift; reads race the DMA), 4 = no index
-// reads inside a row (every step reuses the row's first two pairs), 5 = the
-// products' multiplies dropped (acc += x: half the VALU), 6 = the tails (a
-// row's last np % 4 pairs) skipped.
-// Each row walks its chunk segment in groups of 4 / 2 / 1 entries: the index
-// pairs by uniform ds_read_b128 (segments are padded to even lengths, so two
-// entries share one 16-B LDS read: 2 LDS cycles per entry; ds_read2_b64 took
-// 4), then the gathers, then separately rounded packed mul / add.
-// Tried and dropped (1024 x 101,770; profiles/r02_slab_probe.txt): index by
-// v_readlane from a lane-distributed group index (1.17 ms vs 1.12 with
-// ds_read2_b64 pairs); the wave's entries as one stream in windows of 4 / 8
-// across row boundaries with the accumulator chosen by a uniform switch on a
-// row tag (5.4 ms; needs 8 waves x 16 rows for registers, which slow the rest
-// to 1.5 ms); row pairs in lockstep, 4 entries per row per step, clamped
-// reads, branch-skipped arithmetic (1.73 ms); one stream in steps of up to 4
-// entries of one row with the next step's index read across rows (1.35 ms);
-// index by scalar loads (2.1 ms).  Chunk headers (row starts, the next block's
-// bounds) arrive by vector loads issued with the chunk's DMA, so the chunk
-// loop has no scalar-load waits (1.105-1.12 vs 1.135-1.147 ms with s_load).
+// Each entry pair is one uniform ds_read_b128 of the index (segments are padded
+// to even lengths, so two entries share one 16-B LDS read), two gathers, then
+// separately rounded packed mul / add.  Chunk headers (row starts, the next
+// block's bounds) arrive by vector loads issued with the chunk's DMA, so the
+// chunk loop has no scalar-load waits.
 // Work items: item t = (slab, row group) with t's low 3 bits = the XCD (t & 7),
 // slab = ((t >> 3) / n_rg) * 8 + (t & 7), rg = (t >> 3) % n_rg.  Workgroup b
 // takes items b, b + G, b + 2G, ... (G = gridDim.x, a multiple of 8, so every
@@ -139,19 +152,22 @@ __device__ __forceinline__ uint32_t piece_addr(uint32_t o, uint32_t lb) { return
 // item.  Persistent (G < n_items): the chunk stream runs on across items — the
 // next item's chunk 0 is staged during the current item's last chunk, so a new
 // item does not start on an exposed DMA latency (needs nk >= 2).
-// STREAM (r06, dol_slab_set_variant(2)): each wave walks its run of entry
-// pairs for the chunk as ONE software-pipelined stream instead of a loop per
-// row: the index pair two steps ahead and the gathers one step ahead are in
+// The stream (r06, dol_slab_set_variant(2)): each wave walks its run of entry
+// pairs for the chunk as ONE software-pipelined stream, not a loop per row:
+// the index pair two steps ahead and the gathers one step ahead are in
 // flight while a pair is summed (registers rotate through a 6-step unrolled
 // body, so no copies), and the running sum `a` moves between the wave's 8 row
 // accumulators -- one 32-register tuple -- only at a row boundary, by
 // dynamically indexed register moves (s_set_gpr_idx_on: 4 moves out, 4 in).
-// Per pair: one uniform compare for the boundary; the r03 loop paid a loop
-// entry, tail cases and a prefetch per (row, chunk) segment (~30 instructions
-// per 6.4-entry segment).  Same entries, same order, same bits.  Reads run at
-// most two pairs past the wave's run (kAhead): the index DMA covers them and
-// the packer pads past the last block (slab_tail_kernel).
-template <int PROBE = 0, bool A4 = false, int SV = 0>
+// Per pair: one uniform compare for the boundary.  Same entries, same order,
+// same bits as the row-by-row sum.  Reads run at most two pairs past the
+// wave's run (DOL_SLAB_STREAM_AHEAD = 3 pairs in the asm form; kAhead covers
+// both): the index DMA covers them and the packer pads past the last block
+// (slab_tail_kernel).
+// ASM: the same stream hand-scheduled (csr_slab_stream.inc, variant 3, the
+// default); false: the compiler-scheduled stream above (variant 2, and rows of
+// 2^30 floats and more).
+template <bool ASM>
 __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
     const float* __restrict__ X, int64_t ldx, int x_rows, float* __restrict__ Y, int64_t ldy, int n_rows, int64_t P,
     const int32_t* __restrict__ ent, const int32_t* __restrict__ hdr, int nk, int n_rg, int64_t n_slabs,
@@ -161,10 +177,9 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
   const int64_t p4 = (P + 3) / 4 * 4;  // X rows are readable up to here (dol_hip.h)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // SA (the asm stream, SV 2): DMA addresses as a uniform row base plus this
-  // lane's 32-bit column byte offset (the host keeps round_up(P, 4) * 4 < 2^32),
-  // so an item is uniform state only -- the stream's registers come from here
-  constexpr bool SA = SV == 2;
+  // ASM: DMA addresses as a uniform row base plus this lane's 32-bit column
+  // byte offset (the host keeps round_up(P, 4) * 4 < 2^32), so an item is
+  // uniform state only -- the stream's registers come from here
   struct Item {
     int rg;
     int64_t slab;            // uniform
@@ -179,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
     if (slab >= n_slabs) return false;
     it.rg = int(local % uint32_t(n_rg));
     it.slab = slab;
-    if constexpr (!SA) {
+    if constexpr (!ASM) {
       it.p = slab * kCols + lane * 4;
       const int64_t pl = it.p + 4 <= p4 ? it.p : p4 - 4;  // lanes past P: values unused, reads kept inside round_up(P, 4)
       it.xsrc = X + pl;
@@ -187,7 +202,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
     it.H = hdr + int64_t(it.rg) * nk * (kRows + 1);
     return true;
   };
-  // SA: this lane's in-bounds DMA column of slab `slab`, in bytes
+  // ASM: this lane's in-bounds DMA column of slab `slab`, in bytes
   auto col_bytes = [&](int64_t slab) -> uint32_t {
     const int64_t p = slab * kCols + lane * 4;
     return uint32_t((p + 4 <= p4 ? p : p4 - 4) * 4);
@@ -208,38 +223,36 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
   // costs a null check per use)
   const uint32_t lds_base = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(DOL_LPTR(lds)));
   auto issue = [&](const Item& it, int k, int buf, const Item* after) {
-    if constexpr (PROBE != 2) {
-      // this wave's kPerWave agent pieces of the chunk: one 64-bit product per
-      // chunk, then a row stride per piece (agents past x_rows: the last row
-      // again, never referenced)
-      const int a0w = k * kChunk + wave * kPerWave;
-      const uint32_t la = lds_base + uint32_t(buf * kStage + wave * kPerWave * 1024);
-      if constexpr (SA) {
-        const uint32_t cb = col_bytes(it.slab);
+    // this wave's kPerWave agent pieces of the chunk: one 64-bit product per
+    // chunk, then a row stride per piece (agents past x_rows: the last row
+    // again, never referenced)
+    const int a0w = k * kChunk + wave * kPerWave;
+    const uint32_t la = lds_base + uint32_t(buf * kStage + wave * kPerWave * 1024);
+    if constexpr (ASM) {
+      const uint32_t cb = col_bytes(it.slab);
 #pragma unroll
-        for (int i = 0; i < kPerWave; ++i) {
-          const float* row = X + int64_t(min(a0w + i, x_rows - 1)) * ldx;  // uniform
-          asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(cb), "s"(row), "{m0}"(la + i * 1024) : "memory");
-        }
-      } else if (a0w + kPerWave <= x_rows) {
-        const float* src = it.xsrc + int64_t(a0w) * ldx;
+      for (int i = 0; i < kPerWave; ++i) {
+        const float* row = X + int64_t(min(a0w + i, x_rows - 1)) * ldx;  // uniform
+        asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(cb), "s"(row), "{m0}"(la + i * 1024) : "memory");
+      }
+    } else if (a0w + kPerWave <= x_rows) {
+      const float* src = it.xsrc + int64_t(a0w) * ldx;
 #pragma unroll
-        for (int i = 0; i < kPerWave; ++i)
-          asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src + i * ldx), "{m0}"(la + i * 1024) : "memory");
-      } else {
+      for (int i = 0; i < kPerWave; ++i)
+        asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src + i * ldx), "{m0}"(la + i * 1024) : "memory");
+    } else {
 #pragma unroll
-        for (int i = 0; i < kPerWave; ++i) {
-          const float* src = it.xsrc + int64_t(min(a0w + i, x_rows - 1)) * ldx;
-          asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(la + i * 1024) : "memory");
-        }
+      for (int i = 0; i < kPerWave; ++i) {
+        const float* src = it.xsrc + int64_t(min(a0w + i, x_rows - 1)) * ldx;
+        asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(src), "{m0}"(la + i * 1024) : "memory");
       }
     }
     // the chunk's index block (16-B aligned start, whole 1 KiB pieces; ent is padded)
     const int64_t a0 = int64_t(blk0 & ~1) * 8;  // even: 16-B aligned
     const int64_t nbytes = int64_t(blk1 & ~1) * 8 - a0;
     if (nbytes <= kIdxBytes - kAhead)
-      for (int pc = wave; pc * 1024 < nbytes + (SV ? kAhead : 0); pc += kWaves) {
-        if constexpr (SA) {
+      for (int pc = wave; pc * 1024 < nbytes + kAhead; pc += kWaves) {
+        if constexpr (ASM) {
           const uint32_t la = lds_base + uint32_t(kIdxBase + buf * kIdxBytes + pc * 1024);
           asm volatile("global_load_lds_dwordx4 %0, %1" ::"v"(uint32_t(lane) * 16), "s"(entb + a0 + pc * 1024), "{m0}"(la)
                        : "memory");
@@ -256,10 +269,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
     else if (lane == kRW + 2) hv = hb[kRows];
   };
 
-  f4 acc[kRW];
-#pragma unroll
-  for (int r = 0; r < kRW; ++r) acc[r] = f4{0.f, 0.f, 0.f, 0.f};
-  // STREAM: the row accumulators as one register tuple (dynamic row index ->
+  // the row accumulators as one register tuple (dynamic row index ->
   // s_set_gpr_idx_on moves; a static index is a plain register)
   typedef float v32 __attribute__((ext_vector_type(32)));
   static_assert(kRW * 4 == 32, "the accumulator tuple holds kRW f4 rows");
@@ -282,7 +292,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
     const bool has_nn = has_next && item_at(t + 2 * G, nn);
     for (int k = 0; k < nk; ++k, ++g) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my pieces (and header lanes) of chunk k landed
-      if constexpr (PROBE != 3) __syncthreads();         // ... and every wave's; the other buffer is free
+      __syncthreads();                                   // ... and every wave's; the other buffer is free
       int bnd[kRW + 1];  // header words: (even) first entry | 1 if the row's segment ends in a pad entry
 #pragma unroll
       for (int i = 0; i <= kRW; ++i) bnd[i] = __builtin_amdgcn_readlane(hv, i) & ~1;
@@ -293,34 +303,27 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
       blk1 = __builtin_amdgcn_readlane(hv, kRW + 2);
       if (k + 1 < nk) issue(cur, k + 1, (g + 1) & 1, has_next ? &nxt : nullptr);
       else if (has_next) issue(nxt, 0, (g + 1) & 1, has_nn ? &nn : nullptr);
-      if constexpr (PROBE == 1) continue;
       const uint32_t lb = uint32_t((g & 1) * kStage) + lane16;  // stage base + my lane's 16 B
       auto gather = [&](int32_t o) { return *reinterpret_cast<const f4*>(lds + piece_addr(uint32_t(o), lb)); };
       if (!fits) {  // an over-full block (denser graphs): indices from global memory, same order
 #pragma unroll
         for (int r = 0; r < kRW; ++r) {
-          f4 a = SV ? vget(r) : acc[r];
+          f4 a = vget(r);
           for (int e = bnd[r]; e < bnd[r + 1]; ++e) {
             const int64_t q = int64_t(e >> 1) * 4 + 2 * (e & 1);  // (weight, offset)
             a = fmac(a, __int_as_float(ent[q]), gather(ent[q + 1]));
           }
-          if constexpr (SV != 0) vset(r, a);
-          else acc[r] = a;
+          vset(r, a);
         }
-        if constexpr (SV != 2) continue;  // SV 2: on into the stream with no pairs (one exit for the tuple)
+        if constexpr (!ASM) continue;  // ASM: on into the stream with no pairs (one exit for the tuple)
       }
       // This wave's rows' segments are one contiguous run of entry pairs in the
       // block (row order; every segment an even number of entries, pads
-      // included).  Row r's first two pairs are read while row r - 1 is being
-      // summed (fa / fb), so a row never starts on an index round trip; inside
-      // a row the pairs go two at a time with the next two pairs' index read
-      // behind the current gathers, the loop unrolled twice so the prefetched
-      // index lands in the registers the next step reads (no copies).  Reads
-      // run at most kAhead bytes past the wave's run (inside the stage:
-      // `fits` leaves the room).
+      // included).  Reads run at most kAhead bytes past the wave's run (inside
+      // the stage: `fits` leaves the room).
       const uint32_t ibase = uint32_t(kIdxBase + (g & 1) * kIdxBytes) - uint32_t(e0) * 8;
       auto pair_at = [&](uint32_t a) { return *static_cast<const I4*>(__builtin_assume_aligned(lds + a, 16)); };
-      if constexpr (SV == 2) {  // variant 3: the same stream, hand-scheduled (csr_slab_stream.inc)
+      if constexpr (ASM) {  // variant 3: the stream, hand-scheduled (csr_slab_stream.inc)
         const int b0 = bnd[0];
         const int n = fits ? (bnd[kRW] - b0) >> 1 : 0;  // the stream returns at once on n == 0
         uint32_t pbv = ibase + uint32_t(b0) * 8;  // LDS address of the run's pair 0 (advanced by the loop)
@@ -329,9 +332,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
                      : [acc] DOL_SLAB_STREAM_ACC(accv), [pb] "+v"(pbv), [hc] "+v"(hb)
                      : [lb] "v"(lb), [n] "s"(n), [b0] "s"(b0)
                      : DOL_SLAB_STREAM_CLOBBERS, "scc", "memory");
-        continue;
-      }
-      if constexpr (SV == 1) {
+      } else {
         const int b0 = bnd[0];
         const int n = (bnd[kRW] - b0) >> 1;  // the wave's pairs in this chunk (all rows, pads included)
         if (n == 0) continue;
@@ -378,75 +379,15 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
 #undef DOL_SLAB_STEP
       stream_done:
         vset(r, a);
-        continue;
-      }
-      auto step2 = [&](f4 a, const I4& p, const I4& q) {  // four entries: p's pair, then q's
-        const f4 x0 = gather(p.o0), x1 = gather(p.o1), x2 = gather(q.o0), x3 = gather(q.o1);
-        if constexpr (PROBE == 5) return a + x0 + x1 + x2 + x3;
-        a = fmac(a, __int_as_float(p.w0), x0);
-        a = fmac(a, __int_as_float(p.w1), x1);
-        a = fmac(a, __int_as_float(q.w0), x2);
-        return fmac(a, __int_as_float(q.w1), x3);
-      };
-      I4 fa = pair_at(ibase + uint32_t(bnd[0]) * 8), fb = pair_at(ibase + uint32_t(bnd[0]) * 8 + 16);
-#pragma unroll
-      for (int r = 0; r < kRW; ++r) {
-        int np = (bnd[r + 1] - bnd[r]) >> 1;  // pairs of row r in this chunk
-        I4 qa = fa, qb = fb;
-        if (r + 1 < kRW) {  // the next row's first two pairs
-          const uint32_t nx = ibase + uint32_t(bnd[r + 1]) * 8;
-          fa = pair_at(nx);
-          fb = pair_at(nx + 16);
-        }
-        uint32_t ip = ibase + uint32_t(bnd[r]) * 8 + 32;  // the pair after qb
-        f4 a = acc[r];
-        while (np >= 4) {
-          const I4 na = PROBE == 4 ? qb : pair_at(ip), nb = PROBE == 4 ? qa : pair_at(ip + 16);
-          a = step2(a, qa, qb);
-          // qa / qb are free once this step's products are summed: reload them
-          // only then, into the same registers (a hoisted reload needs fresh
-          // registers and a copy back at the loop end)
-          asm volatile("" : "+v"(a)::"memory");
-          if constexpr (PROBE != 4) {
-            qa = pair_at(ip + 32);
-            qb = pair_at(ip + 48);
-          }
-          ip += 64;
-          a = step2(a, na, nb);
-          asm volatile("" : "+v"(a)::"memory");
-          np -= 4;
-        }
-        if constexpr (PROBE == 6) {  // diagnostics: a row's np % 4 tail pairs skipped
-          acc[r] = a;
-          continue;
-        }
-        if constexpr (A4) {  // np % 4 is 0 or 2 (segments of whole pairs of pairs)
-          if (np >= 2) a = step2(a, qa, qb);
-          acc[r] = a;
-          continue;
-        }
-        if (np >= 2) {
-          I4 na;
-          if (np == 3) na = pair_at(ip);
-          a = step2(a, qa, qb);
-          if (np == 3) {
-            a = fmac(a, __int_as_float(na.w0), gather(na.o0));
-            a = fmac(a, __int_as_float(na.w1), gather(na.o1));
-          }
-        } else if (np == 1) {
-          a = fmac(a, __int_as_float(qa.w0), gather(qa.o0));
-          a = fmac(a, __int_as_float(qa.w1), gather(qa.o1));
-        }
-        acc[r] = a;
       }
     }
-    const int64_t p = SA ? cur.slab * kCols + lane * 4 : cur.p;
+    const int64_t p = ASM ? cur.slab * kCols + lane * 4 : cur.p;
     if (p < P) {
       const int32_t* pr = perm + int64_t(cur.rg) * kRows + row0;
 #pragma unroll
       for (int r = 0; r < kRW; ++r) {
         const int row = pr[r];  // this wave's slot r holds output row `row` (-1: none)
-        const f4 v = SV ? vget(r) : acc[r];
+        const f4 v = vget(r);
         if (row >= 0) {
           float* y = Y + int64_t(row) * ldy + p;
           if (p + 4 <= P) {
@@ -458,8 +399,6 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
       }
     }
     if (!has_next) break;
-#pragma unroll
-    for (int r = 0; r < kRW; ++r) acc[r] = f4{0.f, 0.f, 0.f, 0.f};
     accv = 0.f;
     t += G;
     cur = nxt;
@@ -577,7 +516,7 @@ __global__ __launch_bounds__(256) void slab_count_kernel(const int32_t* __restri
     const int lo = lower_bound_col(col, e0, e1, k * kChunk);
     c = lower_bound_col(col, lo, e1, (k + 1) * kChunk) - lo;
   }
-  hdr[idx] = (c + align - 1) / align * align;  // segments padded to a multiple of `align` (2 or 4)
+  hdr[idx] = (c + align - 1) / align * align;  // segments padded to a multiple of `align` (kSlabAlign)
 }
 
 // in-place exclusive scan of hdr[0..len) (one workgroup: a contiguous segment per thread)
@@ -869,10 +808,11 @@ __global__ __launch_bounds__(64) void slab_scatter_kernel(const int32_t* __restr
 }
 
 // kTailPad pad entries (weight 0, the zero piece) right after the last block:
-// the stream kernel reads up to two pairs past a wave's run, and past the last
-// block ent is otherwise unwritten.  hdr[blocks - 1] (the last group's
+// the stream kernel reads up to DOL_SLAB_STREAM_AHEAD (3) pairs past a wave's
+// run, and past the last block ent is otherwise unwritten.  hdr[blocks - 1] (the last group's
 // terminator slot, count 0) holds the total after the exclusive scan.
 constexpr int kTailPad = 8;
+static_assert(2 * DOL_SLAB_STREAM_AHEAD <= kTailPad, "the tail pads cover the stream's read-ahead (entries)");
 __global__ void slab_tail_kernel(const int32_t* __restrict__ hdr, int64_t blocks, int32_t* __restrict__ ent) {
   const int64_t total = hdr[blocks - 1];
   const int t = threadIdx.x;
@@ -887,35 +827,21 @@ static_assert(kTailPad <= kEntPad, "the tail pads fit the entry slack");
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// kernel of dol_mix_csr_slab_f32 (dol_slab_set_variant): 0 = the process
-// default (DOL_SLAB_KERNEL, else the asm stream), 1 = row loop (r03),
+// kernel of dol_mix_csr_slab_f32 (dol_slab_set_variant): 0 = the default (3),
 // 2 = pipelined stream (r06), 3 = the stream hand-scheduled (asm; rows of
-// 2^30 floats and more run variant 2).  Atomic: thread-compatible like the
-// other setters.
+// 2^30 floats and more run variant 2); 1 was the retired row loop.  Atomic:
+// thread-compatible like the other setters.
 std::atomic<int> g_slab_variant{0};
-int slab_default_variant() {
-  static const int v = [] {
-    const char* e = getenv("DOL_SLAB_KERNEL");
-    const int x = e ? atoi(e) : 3;
-    return (x == 1 || x == 2) ? x : 3;
-  }();
-  return v;
-}
 
-// segment alignment of the packing and the kernel variant that reads it (one
-// value per process): 2 = pairs; 4 = pairs of pairs, so a row's tail is at most
-// one 2-pair step (DOL_SLAB_ALIGN)
-int slab_align() {
-  static const int a = [] { const char* e = getenv("DOL_SLAB_ALIGN"); return (e && atoi(e) == 4) ? 4 : 2; }();
-  return a;
-}
+constexpr int kSlabAlign = 2;  // the packing pads a row's chunk segment to whole pairs
 
 }  // namespace
 
 extern "C" int dol_slab_set_variant(int32_t variant) {
+  if (variant == 1)
+    return dol::fail(DOL_EINVAL, "dol_slab_set_variant: variant 1 (row loop) was retired; use 2 (stream) or 3 (stream, asm)");
   if (variant < 0 || variant > 3)
-    return dol::fail(DOL_EINVAL,
-                     "dol_slab_set_variant: variant %d outside 0 (default) / 1 (row loop) / 2 (stream) / 3 (stream, asm)",
+    return dol::fail(DOL_EINVAL, "dol_slab_set_variant: variant %d outside 0 (default) / 2 (stream) / 3 (stream, asm)",
                      variant);
   const int prev = g_slab_variant.exchange(variant, std::memory_order_relaxed);
   dol::g_err[0] = '\0';
@@ -954,10 +880,8 @@ extern "C" int dol_mix_csr_slab_f32(const float* X, int64_t ldx, int32_t x_rows,
   const int64_t n_slabs = cdiv(P, kCols);
   const int64_t n_items = 8 * cdiv(n_slabs, 8) * n_rg;
   if (n_items >= (int64_t(1) << 32)) return fail(DOL_EINVAL, "dol_mix_csr_slab_f32: too many workgroups");
-  static const int probe = [] { const char* e = getenv("DOL_SLAB_PROBE"); return e ? atoi(e) : 0; }();
-  // persistent grid (one workgroup per CU, a multiple of 8) unless DOL_SLAB_PERSIST=0
-  // or a single chunk (x_rows <= 64: the stream needs nk >= 2)
-  static const int persist = [] { const char* e = getenv("DOL_SLAB_PERSIST"); return e ? atoi(e) : 1; }();
+  // persistent grid (one workgroup per CU, a multiple of 8) unless there is a
+  // single chunk (x_rows <= 64: the stream across items needs nk >= 2)
   static const int n_cu = [] {
     int dev = 0, cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -965,28 +889,15 @@ extern "C" int dol_mix_csr_slab_f32(const float* X, int64_t ldx, int32_t x_rows,
     return cu;
   }();
   const int64_t g_cap = int64_t(n_cu) / 8 * 8;
-  const int64_t grid = (persist && nk >= 2 && g_cap >= 8) ? std::min<int64_t>(n_items, g_cap) : n_items;
+  const int64_t grid = (nk >= 2 && g_cap >= 8) ? std::min<int64_t>(n_items, g_cap) : n_items;
   auto launch = [&](auto kern) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreads), kLds, s, X, ldx, x_rows, Y, ldy,
                        n_rows, P, ent, hdr, nk, static_cast<int>(n_rg), n_slabs, n_items);
   };
-  if (probe == 1) launch(csr_slab_kernel<1>);
-  else if (probe == 2) launch(csr_slab_kernel<2>);
-  else if (probe == 3) launch(csr_slab_kernel<3>);
-  else if (probe == 4) launch(csr_slab_kernel<4>);
-  else if (probe == 5) launch(csr_slab_kernel<5>);
-  else if (probe == 6) launch(csr_slab_kernel<6>);
-  else if (probe == 7) launch(csr_slab_kernel<3, false, 2>);  // the asm stream without the chunk barrier (timing bound; wrong bits)
-  else if (slab_align() == 4) launch(csr_slab_kernel<0, true>);
-  else {
-    int v = g_slab_variant.load(std::memory_order_relaxed);
-    if (v == 0) v = slab_default_variant();
-    if (v == 2) launch(csr_slab_kernel<0, false, 1>);
-    else if (v == 3 && p4 * 4 < (int64_t(1) << 32)) launch(csr_slab_kernel<0, false, 2>);  // 32-bit column offsets
-    else if (v == 3) launch(csr_slab_kernel<0, false, 1>);
-    else launch(csr_slab_kernel<0>);
-  }
+  // the asm stream keeps 32-bit column offsets
+  if (g_slab_variant.load(std::memory_order_relaxed) != 2 && p4 * 4 < (int64_t(1) << 32)) launch(csr_slab_kernel<true>);
+  else launch(csr_slab_kernel<false>);
   return dol::check_launch("dol_mix_csr_slab_f32");
 }
 
@@ -1000,7 +911,7 @@ extern "C" int dol_csr_slab_pack(const int32_t* rowptr, const int32_t* col, cons
   const int64_t len = cdiv(n_rows, kRows) * nk * (kRows + 1);  // the header blocks
   if (cdiv(len, 256) >= (int64_t(1) << 31)) return fail(DOL_EINVAL, "dol_csr_slab_pack: too many chunk blocks");
   hipLaunchKernelGGL(slab_count_kernel, dim3(static_cast<unsigned>(cdiv(len, 256))), dim3(256), 0, s, rowptr, col,
-                     n_rows, nk, len, hdr, slab_align());
+                     n_rows, nk, len, hdr, kSlabAlign);
   const int64_t n_rg = cdiv(n_rows, kRows);
   const int64_t blocks = n_rg * nk * (kRows + 1);  // the header blocks; perm and inv follow
   int32_t* perm = hdr + blocks;
@@ -1021,7 +932,7 @@ extern "C" int dol_csr_slab_pack(const int32_t* rowptr, const int32_t* col, cons
   }
   hipLaunchKernelGGL(slab_scan_kernel, dim3(1), dim3(1024), 0, s, hdr, blocks);
   hipLaunchKernelGGL(slab_scatter_kernel, dim3(static_cast<unsigned>(n_rows)), dim3(64), 0, s, rowptr, col, val, nk,
-                     inv, hdr, ent, slab_align());
+                     inv, hdr, ent, kSlabAlign);
   hipLaunchKernelGGL(slab_tail_kernel, dim3(1), dim3(64), 0, s, hdr, blocks, ent);
   return dol::check_launch("dol_csr_slab_pack");
 }

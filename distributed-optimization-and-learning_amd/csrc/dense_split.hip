@@ -28,13 +28,40 @@
 //
 // GEMM.  256 x 256 output tile per workgroup, 8 waves in 2 x 4, each wave
 // 128 x 64 = 4 x 2 accumulators of 32 x 32 (128 accumulator registers, two
-// waves per SIMD; the r01 form, 4 waves of 128 x 128 with 256 accumulator
-// registers, remains for the narrow tail tiles and DOL_SPLIT3_WAVES=4).
+// waves per SIMD; the r01 form, 4 waves with up to 256 accumulator registers,
+// remains for the narrow tail tiles).
 // K advances 16 per stage (= one MFMA k-step); three stages of 48 KiB in LDS,
 // two in flight while one feeds 48 MFMAs per wave.  Tile
 // order is XCD-aware: workgroup b runs on XCD b % 8, each XCD walks a
 // contiguous range of tiles in groups of 8 row tiles, so the 32 tiles an XCD
 // holds at once share 8 W panels and 4 X panels in its L2.
+//
+// Tried and retired (each was a launch variant behind an environment switch;
+// the code last existed in commit 2d96633):
+//  * DOL_SPLIT3_PROBE 1-7, kernels that skip the staging, the MFMAs or the
+//    stores to bound each part: at 8192 x 101,770 full 53 ms, MFMA-only 45 ms,
+//    staging-only 20 ms (profiles/r01c_dense_split3_probe.txt).  Also tried
+//    there, no gain: fragments double-buffered in registers with the DMA three
+//    stages ahead; v_mfma_f32_16x16x32_bf16 with (k-group, piece pair) k slots
+//    (same speed, and it loses the exactness of x0 + x1 + x2); the DMA issue
+//    sliced between the row blocks' MFMA clusters (53.5-54.1 vs 53.6-53.7 ms).
+//    128-row tiles: 1.27 / 1.40 vs 1.30 ms at 1024 agents, 69-70 vs 58 ms at
+//    8192 (profiles/r01c_dense_split3_tiles.txt): kept 256.
+//  * DOL_SPLIT3_WAVES=4, the 4-wave 256 x 256 main tile: 1.11-1.12 vs
+//    1.07-1.10 ms at 1024 x 101,770, 56.2 vs 54.4-54.5 ms at 8192
+//    (profiles/r02_split3_waves.txt).
+//  * DOL_SPLIT3_FX=1, the r01 fused kernel (2 x 2 waves, X staged as fp32 rows
+//    and split in registers by both row-waves): 68.8 vs 54.4 ms at 8192 x
+//    101,770, 1.45 vs 1.43 ms at 1024 agents against the split pass.
+//  * DOL_SPLIT3_FXW=0 / DOL_SPLIT3_FX8_BATCH, dense_split3_fx8_kernel's 1 x 8
+//    waves as the fused main tile, A fragments read 1 / 2 / 4 blocks at once:
+//    884-887 vs FXW's 864-872 us at 1024 x 101,770
+//    (profiles/r05x_split3_fxw_ab.jsonl).
+//  * DOL_SPLIT3_FX8_TAIL=4, 2 x 2 waves on the fused quarter tiles (4 x 2
+//    stayed).
+//  * DOL_SPLIT3_XPASS1, the r01 X split pass, one thread per (column, k-group):
+//    224 vs 196 us at 1024 x 101,770 (profiles/r02_split3_xpass.txt).
+//  * DOL_SPLIT3_GROUP_M, the row tiles per XCD group (kGroupM = 8 stayed).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -57,11 +84,6 @@ constexpr int kStages = 3;
 constexpr int kLds = kStages * kStageBytes;           // 144 KiB
 constexpr int kGroupM = 8;                            // row tiles per XCD group
 constexpr int kDmaPerWave = kStageBytes / 1024 / 4;   // 12 LDS-DMA instructions per wave per stage
-// fused-X variant: B staged as fp32 rows (16 k x 256 p, 1040-B pitch so the two
-// lane halves' rows 8 apart fall on different banks) and split in registers
-constexpr int kBPitch = 1040;
-constexpr int kStageFX = kOpStage + 16 * kBPitch;     // 41216 B
-constexpr int kDmaFX = (24 + 16) / 4;                  // 10 per wave per stage
 
 #define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -120,25 +142,8 @@ __global__ __launch_bounds__(256) void split3_rows_kernel(const float* __restric
   write_record(v, out + idx * kRec);
 }
 
-// X [K][P] (row stride ldx) -> XB[kg][Pp][48 B]; one thread per (p, kg), p fastest
-// (the r01 pass, DOL_SPLIT3_XPASS1=1; split3_cols4_kernel below is the default:
-// 196 vs 224 us at 1024 x 101,770, profiles/r02_split3_xpass.txt)
-__global__ __launch_bounds__(256) void split3_cols_kernel(const float* __restrict__ X, int64_t ldx, int K, int64_t P,
-                                                          int64_t Pp, int Kg, uint8_t* __restrict__ out) {
-  const int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x;
-  if (idx >= Pp * Kg) return;
-  const int64_t p = idx % Pp;
-  const int kg = int(idx / Pp);
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = 8 * kg + j;
-    v[j] = (p < P && k < K) ? X[int64_t(k) * ldx + p] : 0.f;
-  }
-  write_record(v, out + idx * kRec);
-}
-
-// The same records, one thread per (4 columns, kg): eight 16-B row loads and
+// X [K][P] (row stride ldx) -> XB[kg][Pp][48 B]: one thread per (4 columns, kg),
+// eight 16-B row loads and
 // four whole records.  Thread idx's records are bytes [192 idx, 192 idx + 192)
 // of XB (idx = kg Pp/4 + p/4), so a wave's output is 12 KiB contiguous: the
 // records go through LDS (208-B thread pitch against bank conflicts) and leave
@@ -193,7 +198,7 @@ __device__ __forceinline__ void wait_vmcnt_le(bool more) {
   if (!more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-static_assert(kDmaPerWave == 12 && kDmaFX == 10, "stage sizes changed: recheck the DMA counts per wave");
+static_assert(kDmaPerWave == 12, "stage sizes changed: recheck the DMA counts per wave");
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
@@ -242,45 +247,31 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8& p0, bf16x8& 
   p2 = cat(c);
 }
 
-// PROBE (tools only, DOL_SPLIT3_PROBE): 1 = no operand staging (MFMA ceiling of
-// the loop), 2 = staging only (no fragment reads / MFMAs), 3 = as 1 without
-// the output stores, 4 = full kernel without the output stores (5 / 6 / 7: 1 / 2 /
-// 4 on the 8-wave tiles).  Measured at 8192 x
-// 101770 (profiles/r01c_dense_split3_probe.txt): full 53 ms, MFMA-only 45 ms,
-// staging-only 20 ms.  Tried and dropped (same box, no gain): fragments
-// double-buffered in registers with the DMA three stages ahead; the
-// v_mfma_f32_16x16x32_bf16 shape with (k-group, piece pair) k slots (same
-// speed, and mixing piece scales inside one MFMA loses exactness of x0+x1+x2);
-// the DMA issue sliced between the row blocks' MFMA clusters (sched_barrier
-// fenced; 53.5-54.1 vs 53.6-53.7 ms).  The full kernel's gap to the MFMA-only
-// probe is not an issue-order effect.  128-row tiles (2 stages, two
-// workgroups per CU; or 3 stages): 1.27 / 1.40 vs 1.30 ms at 1024 agents,
-// 69-70 vs 58 ms at 8192 (profiles/r01c_dense_split3_tiles.txt): kept 256.
-// FX: B operand straight from fp32 X (split in registers) instead of the split
-// pass's XB records; X rows readable up to `pread` floats (>= P, % 4 == 0).
-// NB: 32-column blocks per wave along P.  NB = 4 is the 256 x 256 tile; NB = 1
-// / 2 (256 x 64 / 256 x 128 tiles, quarters / halves of a 256 x 256 tile) run
-// the last, partial wave of tiles on four / two times as many CUs.  Every output
-// element sees the same k-steps and the same six MFMAs in the same order
-// under either width, so the two are bit-identical.
+// The split-pass GEMM: both operands as records (WA, XB).
+// NB: 32-column blocks per wave along P.  NB = 1 / 2 with WN = 2 (256 x 64 /
+// 256 x 128 tiles, quarters / halves of a 256 x 256 tile) run the last, partial
+// wave of tiles on four / two times as many CUs.  Every output element sees the
+// same k-steps and the same six MFMAs in the same order under either width, so
+// the two are bit-identical.
 // WN: waves along P (2 x WN waves).  WN = 2: 4 waves, one per SIMD, 128 x 32 NB
-// each (DOL_SPLIT3_WAVES=4, and the narrow tail tiles); WN = 4 (with NB = 2, the
-// default for 256 x 256 tiles): 8 waves, two per SIMD, 128 x 64 each, so one
-// wave's LDS-DMA issue and fragment reads overlap the other's MFMAs.
-template <int PROBE, bool FX, int NB = 4, int WN = 2>
+// each (the narrow tail tiles); WN = 4 (with NB = 2, the 256 x 256 tiles): 8
+// waves, two per SIMD, 128 x 64 each, so one wave's LDS-DMA issue and fragment
+// reads overlap the other's MFMAs.
+// X, ldx, K and pread are unused here: they stay so the kernarg layout is the
+// fused kernels' (and the parent's).
+template <int NB, int WN>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2)))
 void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restrict__ XB, float* __restrict__ Y,
                          int64_t ldy, int M, int64_t P, int64_t Mp, int64_t Pp, int n_stages, int n_mt,
                          int64_t n_pt, int64_t tiles_per_xcd, int group_m, const float* __restrict__ X,
                          int64_t ldx, int K, int64_t pread, int64_t t_base, int64_t t_end) {
-  static_assert((WN == 2 && (NB == 4 || ((NB == 1 || NB == 2) && !FX && PROBE == 0))) ||
-                    (WN == 4 && NB == 2 && !FX),
-                "tiles: 256 x 256 (4 or 8 waves) or narrow split-pass tiles");
+  static_assert((WN == 2 && (NB == 1 || NB == 2)) || (WN == 4 && NB == 2),
+                "tiles: 256 x 256 (8 waves) or narrow tail tiles (4 waves)");
   constexpr int kWaves = 2 * WN;
   constexpr int BN = 32 * NB * WN;                         // tile width along P
   constexpr int kParts = kTile / BN;                       // narrow tiles per 256-wide tile
-  constexpr int kStage = FX ? kStageFX : kOpStage + 2 * BN * kRec;
-  constexpr int kDmaTot = FX ? 4 * kDmaFX : 24 + 3 * BN / 32;  // 1-KiB DMA pieces per stage
+  constexpr int kStage = kOpStage + 2 * BN * kRec;
+  constexpr int kDmaTot = 24 + 3 * BN / 32;                // 1-KiB DMA pieces per stage
   constexpr int kDma = (kDmaTot + kWaves - 1) / kWaves;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   int64_t t;
@@ -313,24 +304,15 @@ void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restri
   const uint8_t* srcB = XB + col0 * kRec + lane * 16;
   const int64_t pitchA = Mp * kRec, pitchB = Pp * kRec;  // bytes per k-group
   auto issue = [&](int s) {
-    if constexpr (PROBE == 1 || PROBE == 3) return;
     uint8_t* st = lds + (s % kStages) * kStage;
 #pragma unroll
     for (int i = 0; i < kDma; ++i) {
-      const int q = wave + kWaves * i;  // 1 KiB each (A records) / one fp32 row of 256 p (FX B)
+      const int q = wave + kWaves * i;  // 1 KiB each
       if (kDmaTot % kWaves && q >= kDmaTot) continue;
-      if (!FX && kParts != 1 && q >= 24) {  // narrow B: 3 * NB pieces per k-group
+      if (kParts != 1 && q >= 24) {  // narrow B: 3 * NB pieces per k-group
         const int qb = q - 24, kgl = qb / (3 * NB), chunk = qb % (3 * NB);
         const uint8_t* src = srcB + (2 * int64_t(s) + kgl) * pitchB + chunk * 1024;
         __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(st + q * 1024), 16, 0, 0);
-        continue;
-      }
-      if (FX && q >= 24) {
-        const int k = min(16 * s + (q - 24), K - 1);     // rows past K: masked after the read
-        int64_t c = pt * kTile + lane * 4;
-        if (c + 4 > pread) c = pread - 4;                // columns past P: masked after the read
-        __builtin_amdgcn_global_load_lds(DOL_GPTR(X + int64_t(k) * ldx + c), DOL_LPTR(st + kOpStage + (q - 24) * kBPitch),
-                                         16, 0, 0);
         continue;
       }
       const int op = q / 24, qq = q % 24, kgl = qq / 12, chunk = qq % 12;
@@ -355,29 +337,11 @@ void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restri
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int p = 0; p < 3; ++p) fa[i][p] = *reinterpret_cast<const bf16x8*>(sa + i * 32 * kRec + 16 * p);
-    if constexpr (FX) {
-      const float* bs = reinterpret_cast<const float*>(st + kOpStage) + 8 * h * (kBPitch / 4);
-      const bool edge = (pt == n_pt - 1) || (16 * s + 16 > K);  // wave-uniform
+    const uint8_t* sb = st + kOpStage + h * (BN * kRec) + (wn * 32 * NB + li) * kRec;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int pl = wn * 128 + i * 32 + li;
-        float v[8];
+    for (int i = 0; i < NB; ++i)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = bs[j * (kBPitch / 4) + pl];
-        if (edge) {
-          const bool pin = pt * kTile + pl < P;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = (pin && 16 * s + 8 * h + j < K) ? v[j] : 0.f;
-        }
-        split8(v, fb[i][0], fb[i][1], fb[i][2]);
-      }
-    } else {
-      const uint8_t* sb = st + kOpStage + h * (BN * kRec) + (wn * 32 * NB + li) * kRec;
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) fb[i][p] = *reinterpret_cast<const bf16x8*>(sb + i * 32 * kRec + 16 * p);
-    }
+      for (int p = 0; p < 3; ++p) fb[i][p] = *reinterpret_cast<const bf16x8*>(sb + i * 32 * kRec + 16 * p);
   };
   // the six piece products of one 32x32x16 block, smallest first
   auto mfmas = [&](const bf16x8 (&fa)[4][3], const bf16x8 (&fb)[NB][3]) {
@@ -408,7 +372,6 @@ void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restri
     wait_vmcnt_le<kDmaTot / kWaves>(s + 1 < n_stages);  // my DMA of stage s landed (the fewest any wave issues)
     barrier();                           // ... and every wave's; stage (s + 2) % 3 is free
     if (s + 2 < n_stages) issue(s + 2);
-    if constexpr (PROBE == 2) continue;
     bf16x8 fa[4][3], fb[NB][3];
     read_frags(s, fa, fb);
     mfmas(fa, fb);
@@ -422,8 +385,7 @@ void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restri
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int row = mt * kTile + wm * 128 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (row < M && col < P && (PROBE < 3 || M < 0))  // probes 3/4 drop the stores (M < 0 never holds)
-          __builtin_nontemporal_store(acc[a][b][e], Y + int64_t(row) * ldy + col);
+        if (row < M && col < P) __builtin_nontemporal_store(acc[a][b][e], Y + int64_t(row) * ldy + col);
       }
     }
 }
@@ -442,14 +404,13 @@ void dense_split3_kernel(const uint8_t* __restrict__ WA, const uint8_t* __restri
 //     both waves of a SIMD waited on the reads and the split together, 1.011
 //     vs 1.045 ms for the split pass + record GEMM, profiles/r05h_split3_ab.jsonl);
 //   * runs its 8 row blocks' six MFMAs, A fragments read block by block.
-// The r01 FX kernel's 2 x 2 waves split every B value twice and four column
-// blocks per wave.  Each output element sees the same k-steps and the same
-// six MFMAs in the same order as dense_split3_kernel: bit-identical.
+// Each output element sees the same k-steps and the same six MFMAs in the
+// same order as dense_split3_kernel: bit-identical.
 // RW x CW waves, wave (wm, wn) = rows [256 / RW * wm, + 256 / RW) x 32 columns
-// at 32 wn: <1, 8> = 256 x 256 tiles, 8 waves (two per SIMD); <4, 2> = the
-// 256 x 64 quarter tiles of the last, partial wave of tiles, also 8 waves
-// (the four row-waves of a column each stage and split their own copy of
-// its X slice, so no wave waits on another's B).
+// at 32 wn.  In use: <4, 2>, the 256 x 64 quarter tiles of the last, partial
+// wave of tiles, 8 waves (the four row-waves of a column each stage and split
+// their own copy of its X slice, so no wave waits on another's B).  The 256 x
+// 256 main tiles run dense_split3_fxw_kernel below (<1, 8> here was retired).
 template <int RW, int CW>
 struct Fx8Geom {
   static constexpr int kWaves = RW * CW;
@@ -462,7 +423,7 @@ struct Fx8Geom {
   static_assert(24 % kWaves == 0 && 8 % RW == 0, "A pieces / row blocks must split evenly over the waves");
 };
 
-template <int RW, int CW, int BATCH = 1>
+template <int RW, int CW>
 __global__ __launch_bounds__(64 * RW * CW)
 __attribute__((amdgpu_waves_per_eu(RW * CW >= 8 ? RW * CW / 4 : 1, RW * CW >= 8 ? RW * CW / 4 : 1)))
 void dense_split3_fx8_kernel(const uint8_t* __restrict__ WA, float* __restrict__ Y, int64_t ldy, int M, int64_t P,
@@ -567,30 +528,21 @@ void dense_split3_fx8_kernel(const uint8_t* __restrict__ WA, float* __restrict__
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    // A fragments: BATCH = 1 double-buffers single blocks (block a + 1's reads
-    // in flight while block a's MFMAs issue); BATCH > 1 reads BATCH blocks'
-    // fragments at once and then runs their MFMAs (one LDS wait per batch).
-    // The scheduler otherwise sinks each read to its use and waits
-    // lgkmcnt(0) before every block's six MFMAs: sched_barrier keeps the
-    // reads where they are written.
-    constexpr int NQ = BATCH == 1 ? 2 : BATCH;
-    bf16x8 fq[NQ][3];
+    // A fragments double-buffered by single blocks (block a + 1's reads in
+    // flight while block a's MFMAs issue).  The scheduler otherwise sinks each
+    // read to its use and waits lgkmcnt(0) before every block's six MFMAs:
+    // sched_barrier keeps the reads where they are written.
+    bf16x8 fq[2][3];
     auto read_block = [&](int a, bf16x8 (&f)[3]) {
 #pragma unroll
       for (int p = 0; p < 3; ++p) f[p] = *reinterpret_cast<const bf16x8*>(sa + a * 32 * kRec + 16 * p);
     };
-    if constexpr (BATCH == 1) read_block(0, fq[0]);
+    read_block(0, fq[0]);
 #pragma unroll
     for (int a = 0; a < Gm::kRB; ++a) {
-      if constexpr (BATCH == 1) {
-        if (a + 1 < Gm::kRB) read_block(a + 1, fq[(a + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-      } else if (a % BATCH == 0) {
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) read_block(a + u, fq[u]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const bf16x8 (&fa)[3] = fq[BATCH == 1 ? (a & 1) : (a % BATCH)];
+      if (a + 1 < Gm::kRB) read_block(a + 1, fq[(a + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 (&fa)[3] = fq[a & 1];
       f32x16 c = acc[a];  // the six piece products of one 32x32x16 block, smallest first (as dense_split3_kernel)
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], c, 0, 0, 0);
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], c, 0, 0, 0);
@@ -634,18 +586,15 @@ inline Split3Geom geom(int32_t M, int32_t K, int64_t P) {
   return g;
 }
 
-// The in-register X split (FX kernel, opt-in with DOL_SPLIT3_FUSE_X) needs whole
-// 16-B pieces of X rows: rows 16-B aligned, ldx % 4 == 0 and readable up to
-// round_up(P, 4) floats — always so when P % 4 == 0, and asserted by the caller
-// with DOL_SPLIT3_X_ROWS_PADDED.  It needs no X workspace (0.40 vs 5.4 GB at
-// 8192 x 101,770) but runs slower: 68.8 vs 54.4 ms there, 1.45 vs 1.43 ms at
-// 1024 agents (each B value is split by both row-waves, 32 ds_read_b32 + ~250
-// VALU per stage and wave beside the 96 MFMAs) — the split pass is the default.
+// The in-register X split (the fused kernels, opt-in with DOL_SPLIT3_FUSE_X)
+// needs whole 16-B pieces of X rows: rows 16-B aligned, ldx % 4 == 0 and
+// readable up to round_up(P, 4) floats — always so when P % 4 == 0, and
+// asserted by the caller with DOL_SPLIT3_X_ROWS_PADDED.  It needs no X
+// workspace (0.40 vs 5.4 GB at 8192 x 101,770).
 inline bool fused_x_ok(const float* X, int64_t ldx, int64_t P, int flags) {
   const bool aligned = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 4 == 0;
   return (flags & DOL_SPLIT3_FUSE_X) && aligned && P >= 4 && (P % 4 == 0 || (flags & DOL_SPLIT3_X_ROWS_PADDED));
 }
-
 
 // FXW (r05): the split-pass kernel's 2 x 4 waves and fragment reads (12 A + 6
 // B ds_read_b128 per wave and k-step, the fewest of any layout), with the B
@@ -855,28 +804,14 @@ extern "C" int dol_mix_dense_split3_f32(const float* W, int64_t ldw, const float
   if (!fx) {
     const int64_t n = g.Pp * g.Kg;
     if (cdiv(n, 256) >= (int64_t(1) << 32)) return fail(DOL_EINVAL, "dol_mix_dense_split3_f32: X too large");
-    static const bool per_column = getenv("DOL_SPLIT3_XPASS1") != nullptr;  // diagnostic: the r01 pass
     const bool vec = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ldx % 4 == 0;
-    if (per_column)
-      hipLaunchKernelGGL(split3_cols_kernel, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, s, X, ldx, K, P,
-                         g.Pp, static_cast<int>(g.Kg), xb);
-    else if (vec)
+    if (vec)
       hipLaunchKernelGGL(split3_cols4_kernel<true>, dim3(static_cast<unsigned>(cdiv(n / 4, 256))), dim3(256), 0, s, X,
                          ldx, K, P, g.Pp, static_cast<int>(g.Kg), xb);
     else
       hipLaunchKernelGGL(split3_cols4_kernel<false>, dim3(static_cast<unsigned>(cdiv(n / 4, 256))), dim3(256), 0, s, X,
                          ldx, K, P, g.Pp, static_cast<int>(g.Kg), xb);
   }
-  // diagnostics knobs (tools/gpu_dense_probe.sh); read once per process
-  static const int probe = [] { const char* e = getenv("DOL_SPLIT3_PROBE"); return e ? atoi(e) : 0; }();
-  // 8 waves (two per SIMD) unless DOL_SPLIT3_WAVES=4: 1.07-1.10 vs 1.11-1.12 ms at
-  // 1024 x 101,770, 54.4-54.5 vs 56.2 ms at 8192 (profiles/r02_split3_waves.txt);
-  // same bits (tests/test_kernels_gpu.py split3 tests under both)
-  static const bool waves8 = [] { const char* e = getenv("DOL_SPLIT3_WAVES"); return !(e && atoi(e) == 4); }();
-  static const int group_m = [] {
-    const char* e = getenv("DOL_SPLIT3_GROUP_M");
-    return e && atoi(e) > 0 ? atoi(e) : kGroupM;
-  }();
   const int n_mt = static_cast<int>(g.Mp / kTile);
   const int64_t n_pt = g.Pp / kTile;
   const int64_t n_tiles = int64_t(n_mt) * n_pt;
@@ -895,68 +830,38 @@ extern "C" int dol_mix_dense_split3_f32(const float* W, int64_t ldw, const float
   const char* cus_env = getenv("DOL_SPLIT3_CUS");
   const int64_t cus = cus_env && *cus_env ? atoi(cus_env) : n_cu;
   const int64_t tail = cus > 0 ? n_tiles % cus : 0;
-  // FUSE_X runs dense_split3_fx8_kernel (r05) unless DOL_SPLIT3_FX=1 asks for the r01 in-register kernel
-  static const bool fx_old = [] { const char* e = getenv("DOL_SPLIT3_FX"); return e && atoi(e) == 1; }();
-  const bool fx8 = fx && !fx_old && probe == 0;
-  const bool fx8_tail = fx8 && n_tiles > cus && tail > 0 && 4 * tail <= cus;  // 256 x 64 quarters, one CU each
-  const bool narrow_tail = (!fx && probe == 0 && n_tiles > cus && tail > 0 && 2 * tail <= cus) || fx8_tail;
-  const int nb_tail = 4 * tail <= cus ? 1 : 2;
+  // the fused path's tail is quarters only (256 x 64, one CU each); the split pass also takes halves
+  const bool narrow_tail = n_tiles > cus && tail > 0 && (fx ? 4 : 2) * tail <= cus;
   const int64_t t_main = narrow_tail ? n_tiles - tail : n_tiles;
   const int64_t tiles_per_xcd = cdiv(t_main, 8);
   if (8 * tiles_per_xcd >= (int64_t(1) << 32) || 4 * tail >= (int64_t(1) << 32))
     return fail(DOL_EINVAL, "dol_mix_dense_split3_f32: too many tiles");
   const int64_t pread = (P % 4 == 0) ? P : (P + 3) / 4 * 4;
-  auto launch = [&](auto kern, int lds, int64_t grid, int64_t t_base, int64_t t_end, int threads = 256) {
-    // > 64 KiB of dynamic LDS: set on every call (cheap), so every device of the process gets it
+  const int n_stages = static_cast<int>(g.Kg / 2);
+  // > 64 KiB of dynamic LDS: set on every call (cheap), so every device of the process gets it
+  auto max_lds = [](auto kern, int lds) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, wa, xb, Y, ldy, M,
-                       P, g.Mp, g.Pp, static_cast<int>(g.Kg / 2), n_mt, n_pt, tiles_per_xcd, group_m, X, ldx, K,
-                       pread, t_base, t_end);
   };
-  const int64_t grid = 8 * tiles_per_xcd;
-  if (fx8) {
-    auto launch8 = [&](auto kern, int lds, int64_t grd, int64_t t_base, int64_t t_end, int threads) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grd)), dim3(threads), lds, s, wa, Y, ldy, M, P, g.Mp,
-                         static_cast<int>(g.Kg / 2), n_mt, n_pt, tiles_per_xcd, group_m, X, ldx, K, pread, t_base,
-                         t_end);
-    };
-    // DOL_SPLIT3_FX8_BATCH (read per call; A fragment batching, same bits): 1 (default), 2 or 4
-    const char* be = getenv("DOL_SPLIT3_FX8_BATCH");
-    const int batch = be ? atoi(be) : 1;
-    // main tiles: dense_split3_fxw_kernel (r05; 864-872 vs 884-887 us for FX8's 1 x 8 layout at
-    // 1024 x 101,770, profiles/r05x_split3_fxw_ab.jsonl) unless DOL_SPLIT3_FXW=0 (read per call; same bits)
-    const char* we = getenv("DOL_SPLIT3_FXW");
-    if (!(we && atoi(we) == 0)) launch8(dense_split3_fxw_kernel, kFxwLds, grid, 0, t_main, 512);
-    else if (batch == 4) launch8(dense_split3_fx8_kernel<1, 8, 4>, kStages * Fx8Geom<1, 8>::kStage, grid, 0, t_main, 512);
-    else if (batch == 2) launch8(dense_split3_fx8_kernel<1, 8, 2>, kStages * Fx8Geom<1, 8>::kStage, grid, 0, t_main, 512);
-    else launch8(dense_split3_fx8_kernel<1, 8>, kStages * Fx8Geom<1, 8>::kStage, grid, 0, t_main, 512);
-    // the tail's quarter tiles: DOL_SPLIT3_FX8_TAIL (read per call; same bits) 8 = 4 x 2 waves (default), 4 = 2 x 2
-    const char* te = getenv("DOL_SPLIT3_FX8_TAIL");
-    if (fx8_tail && te && atoi(te) == 4)
-      launch8(dense_split3_fx8_kernel<2, 2>, kStages * Fx8Geom<2, 2>::kStage, 4 * tail, t_main, n_tiles, 256);
-    else if (fx8_tail)
-      launch8(dense_split3_fx8_kernel<4, 2>, kStages * Fx8Geom<4, 2>::kStage, 4 * tail, t_main, n_tiles, 512);
-    return dol::check_launch("dol_mix_dense_split3_f32");
+  auto launch_fused = [&](auto kern, int lds, int64_t grid, int64_t t_base, int64_t t_end) {
+    max_lds(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(512), lds, s, wa, Y, ldy, M, P, g.Mp, n_stages,
+                       n_mt, n_pt, tiles_per_xcd, kGroupM, X, ldx, K, pread, t_base, t_end);
+  };
+  auto launch_split = [&](auto kern, int lds, int64_t grid, int64_t t_base, int64_t t_end, int threads) {
+    max_lds(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(threads), lds, s, wa, xb, Y, ldy, M, P, g.Mp,
+                       g.Pp, n_stages, n_mt, n_pt, tiles_per_xcd, kGroupM, X, ldx, K, pread, t_base, t_end);
+  };
+  if (fx) {  // FXW main tiles, FX8 quarter tail
+    launch_fused(dense_split3_fxw_kernel, kFxwLds, 8 * tiles_per_xcd, 0, t_main);
+    if (narrow_tail)
+      launch_fused(dense_split3_fx8_kernel<4, 2>, kStages * Fx8Geom<4, 2>::kStage, 4 * tail, t_main, n_tiles);
+  } else {  // 2 x 4-wave main tiles, 4-wave quarter / half tail
+    launch_split(dense_split3_kernel<2, 4>, kLds, 8 * tiles_per_xcd, 0, t_main, 512);
+    if (narrow_tail && 4 * tail <= cus)
+      launch_split(dense_split3_kernel<1, 2>, kStages * (kOpStage + 2 * 64 * kRec), 4 * tail, t_main, n_tiles, 256);
+    else if (narrow_tail)
+      launch_split(dense_split3_kernel<2, 2>, kStages * (kOpStage + 2 * 128 * kRec), 2 * tail, t_main, n_tiles, 256);
   }
-  if (fx) {
-    if (probe == 1) launch(dense_split3_kernel<1, true>, kStages * kStageFX, grid, 0, t_main);
-    else if (probe == 2) launch(dense_split3_kernel<2, true>, kStages * kStageFX, grid, 0, t_main);
-    else launch(dense_split3_kernel<0, true>, kStages * kStageFX, grid, 0, t_main);
-  } else {
-    if (probe == 1) launch(dense_split3_kernel<1, false>, kLds, grid, 0, t_main);
-    else if (probe == 2) launch(dense_split3_kernel<2, false>, kLds, grid, 0, t_main);
-    else if (probe == 3) launch(dense_split3_kernel<3, false>, kLds, grid, 0, t_main);
-    else if (probe == 4) launch(dense_split3_kernel<4, false>, kLds, grid, 0, t_main);
-    else if (waves8 && probe == 0) launch(dense_split3_kernel<0, false, 2, 4>, kLds, grid, 0, t_main, 512);
-    else if (waves8 && probe == 5) launch(dense_split3_kernel<1, false, 2, 4>, kLds, grid, 0, t_main, 512);
-    else if (waves8 && probe == 6) launch(dense_split3_kernel<2, false, 2, 4>, kLds, grid, 0, t_main, 512);
-    else if (waves8 && probe == 7) launch(dense_split3_kernel<4, false, 2, 4>, kLds, grid, 0, t_main, 512);
-    else launch(dense_split3_kernel<0, false>, kLds, grid, 0, t_main);
-  }
-  if (narrow_tail && nb_tail == 1)
-    launch(dense_split3_kernel<0, false, 1>, kStages * (kOpStage + 2 * 64 * kRec), 4 * tail, t_main, n_tiles);
-  else if (narrow_tail)
-    launch(dense_split3_kernel<0, false, 2>, kStages * (kOpStage + 2 * 128 * kRec), 2 * tail, t_main, n_tiles);
   return dol::check_launch("dol_mix_dense_split3_f32");
 }

@@ -26,6 +26,20 @@
 // (DIST/clients.py:61-69).  Stores are buffer stores with dropped
 // out-of-range lanes, so every thread issues the same number of VMEM ops per
 // stage and the counted wait is exact.
+//
+// Tried and retired (each was a launch variant behind an environment switch;
+// the code last existed in commit 2d96633):
+//  * DOL_PM_DGD_GEOM, the fused round's stage geometry forced to 64 KiB x 2,
+//    48 KiB x 3 or 80 KiB x 2: at 1024 x 2^20 rr4, least squares + momentum
+//    3.45 ms on 80 KiB x 2 vs 3.56 (64 KiB x 2) and 3.49 (48 KiB x 3);
+//    logistic, no momentum, 2.25 on 64 KiB x 2 vs 2.43 / 2.55.  Each mode now
+//    has the geometry that won: 80 KiB x 2 with the momentum read (mode 2),
+//    64 KiB x 2 without.
+//  * DOL_PM_BIG_NB=4, four 32-KiB buffers beyond 4096 agents (r01); five won
+//    (profiles/r02_pm_nbuf.txt).
+//  * DOL_PM_VARIANT 1 / 4, the plain mix with default-policy (not
+//    nontemporal) LDS-DMA loads, and a copy y = x in the same geometry (the
+//    structure's own ceiling): measurement only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,7 +47,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <type_traits>
 
 #include "../../include/dol_hip.h"
 #include "dol_common.h"
@@ -52,6 +65,7 @@ using rsrc_t = __amdgpu_buffer_rsrc_t;
 constexpr int kMaxAgents = 8192;          // one p-row image fits a 32 KiB stage
 constexpr int kT1 = 1024;                 // threads per workgroup (16 waves, one workgroup per CU)
 constexpr uint32_t kOOB = 0x80000000u;    // a buffer offset past every range: the store is dropped
+constexpr int kNT = 2;                    // cache-policy bits of the LDS-DMA loads and the stores: nontemporal
 
 __device__ __forceinline__ void wait_vmcnt(int n) {
   switch (n) {
@@ -175,14 +189,13 @@ __device__ __forceinline__ float dgd_local(float x, float t, float& b, const PmD
 // its rows of YT (and, OBJ >= 0, run the local steps first: target / momentum
 // images of nw floats per p-row follow the X image): spt (x2 with a momentum
 // store) buffer stores per thread, out-of-range ones dropped.
-template <int T, int QPT, int SAUX, bool COPY, int OBJ = -1, int MODE = 0>
+template <int T, int QPT, int OBJ = -1, int MODE = 0>
 __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __restrict__ im0, float* __restrict__ YT,
                                           int64_t ldy, int n_rows, int64_t P, int64_t p0, int xw, int sr, int spt,
                                           int q0, int g, int GR, const int32_t* __restrict__ rowptr,
                                           const int32_t* __restrict__ col, const float* __restrict__ val,
                                           const PmDgd& e, int nw) {
   const int nq = (n_rows + 3) / 4;
-  const int xq = xw / 4;
   const int64_t rows_here = std::min<int64_t>(sr, P - p0);
   const rsrc_t ry = make_rsrc(YT + p0 * ldy, static_cast<uint32_t>(rows_here * ldy * 4));
   rsrc_t rm = ry;
@@ -197,7 +210,7 @@ __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __r
 #pragma unroll
     for (int j = 0; j < QPT; ++j) {
       const int q = q0 + j * T;
-      f4 y = COPY ? *reinterpret_cast<const f4*>(im + 4 * (q % xq)) : mix_quad(Q[j], im, q, rowptr, col, val);
+      f4 y = mix_quad(Q[j], im, q, rowptr, col, val);
       f4 bv = f4{0.f, 0.f, 0.f, 0.f};
       if constexpr (OBJ >= 0) {
         const int qc = q < nq ? q : 0;
@@ -213,25 +226,25 @@ __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __r
       constexpr bool kMom = OBJ >= 0 && MODE != 0;
       if (4 * q + 3 < n_rows || q >= nq) {  // whole quad, or none (dropped)
         const bool ok = prow_ok && q < nq;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, y), ry, ok ? off : kOOB, 0, SAUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, y), ry, ok ? off : kOOB, 0, kNT);
         if constexpr (kMom)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, bv), rm, ok ? offm : kOOB, 0, SAUX);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, bv), rm, ok ? offm : kOOB, 0, kNT);
       } else {  // the ragged last quad (elements named one by one: hipcc 7.2 stored
                 // element 0 four times from a loop over y[a] here)
         const float ye[4] = {y.x, y.y, y.z, y.w};
         const int left = n_rows - 4 * q;  // 1..3
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ye[0]), ry, prow_ok ? off : kOOB, 0, SAUX);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ye[0]), ry, prow_ok ? off : kOOB, 0, kNT);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ye[1]), ry, prow_ok && left > 1 ? off + 4 : kOOB, 0,
-                                              SAUX);
+                                              kNT);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ye[2]), ry, prow_ok && left > 2 ? off + 8 : kOOB, 0,
-                                              SAUX);
+                                              kNT);
         if constexpr (kMom) {
           const float be[4] = {bv.x, bv.y, bv.z, bv.w};
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(be[0]), rm, prow_ok ? offm : kOOB, 0, SAUX);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(be[0]), rm, prow_ok ? offm : kOOB, 0, kNT);
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(be[1]), rm, prow_ok && left > 1 ? offm + 4 : kOOB, 0,
-                                                SAUX);
+                                                kNT);
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(be[2]), rm, prow_ok && left > 2 ? offm + 8 : kOOB, 0,
-                                                SAUX);
+                                                kNT);
         }
       }
     }
@@ -239,12 +252,10 @@ __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __r
 }
 
 // T threads per workgroup, SF floats per stage buffer, NBUF buffers, QPT
-// quads per thread.  LAUX / SAUX: cache-policy bits of the LDS-DMA loads / the
-// stores (0 default, 2 nontemporal); COPY: y = x of the same agent (a copy in
-// the same geometry: the structure's own ceiling, measurement only).
+// quads per thread.
 // OBJ >= 0: the config-3 epilogue (PmDgd), its target (+ momentum) p-rows
 // staged behind X's in every stage (nw floats each).
-template <int T, int SF, int NBUF, int QPT, int LAUX, int SAUX, bool COPY = false, int OBJ = -1, int MODE = 0>
+template <int T, int SF, int NBUF, int QPT, int OBJ = -1, int MODE = 0>
 __global__ __launch_bounds__(T) void csr_pm_kernel(const float* __restrict__ XT, int64_t ldx, int x_rows,
                                                    float* __restrict__ YT, int64_t ldy, int n_rows, int64_t P,
                                                    int xw, int sr, int qp_log2, int spt, int64_t n_stages, int nseg,
@@ -299,7 +310,7 @@ __global__ __launch_bounds__(T) void csr_pm_kernel(const float* __restrict__ XT,
         if ((op == 0 || (MODE == 2 && op == 1)) && p0 + pr < P && j4 < nr4)
           src = op == 0 ? e.T + (p0 + pr) * e.ldt + 4 * j4 : e.M + (p0 + pr) * e.ldm + 4 * j4;
       }
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, LAUX);
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, kNT);
     }
   };
   constexpr int kStores = (OBJ >= 0 && MODE != 0) ? 2 : 1;  // buffer stores per (p-row, quad)
@@ -320,8 +331,7 @@ __global__ __launch_bounds__(T) void csr_pm_kernel(const float* __restrict__ XT,
     if (k + NBUF - 1 < nk) issue(k + NBUF - 1);
     const int64_t p0 = stage_of(k) * sr;
     const float* im0 = img + (k % NBUF) * SF;
-    mix_stage<T, QPT, SAUX, COPY, OBJ, MODE>(Q, im0, YT, ldy, n_rows, P, p0, xw, sr, spt, q0, g, GR, rowptr, col, val,
-                                            e, nw);
+    mix_stage<T, QPT, OBJ, MODE>(Q, im0, YT, ldy, n_rows, P, p0, xw, sr, spt, q0, g, GR, rowptr, col, val, e, nw);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this stage's LDS reads are done before the next barrier
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -428,17 +438,12 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   // one stage per short-lived workgroup 4.4; a per-wave ring (no workgroup
   // barrier, 4 KiB p-rows, 176 VGPRs) 1.64.
   const bool big = nq > kT1 || xw > 4096;
-  // fused round: 64 KiB x 2 stages, or 80 KiB x 2 with the momentum read (1024
-  // x 2^20 rr4, one box, twice: least squares + momentum 3.45 ms vs 3.56 with
-  // 64 KiB x 2 and 3.49 with 48 KiB x 3; logistic, no momentum, 2.25 vs 2.43 /
-  // 2.55).  DOL_PM_DGD_GEOM (0 / 1 / 2) overrides, for measurement.
-  const int dgeo = obj >= 0 ? env_int("DOL_PM_DGD_GEOM", ne == 2 ? 2 : 0) : 0;
-  const int SF = big ? 8192 : (dgeo == 1 ? 12288 : dgeo == 2 ? 20480 : 16384);
-  // beyond 4096 agents: five 32-KiB buffers (all 160 KiB, four p-rows in flight)
-  // (profiles/r02_pm_nbuf.txt); DOL_PM_BIG_NB=4 keeps four.  At <= 4096 agents
+  // fused round (<= 4096 agents): 64 KiB x 2 stages, or 80 KiB x 2 with the
+  // momentum read (mode 2).  Beyond 4096 agents: five 32-KiB buffers (all 160
+  // KiB, four p-rows in flight; profiles/r02_pm_nbuf.txt).  At <= 4096 agents
   // 5 x 32 KiB ran level with 2 x 64 KiB (1.56-1.59 ms at 1024 x 2^20)
-  static const int big_nb = env_int("DOL_PM_BIG_NB", 5) == 4 ? 4 : 5;
-  const int NB = big ? big_nb : (dgeo == 1 ? 3 : 2);  // must match the kernel's NBUF (LDS size)
+  const int SF = big ? 8192 : (ne == 2 ? 20480 : 16384);
+  const int NB = big ? 5 : 2;  // must match the kernel's NBUF (LDS size)
   int sr = SF / (xw + ne * nw);
   int qp_log2 = 0, spt;
   if (!big) {
@@ -456,9 +461,6 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   const int64_t n_stages = (P + sr - 1) / sr;
   const int ncu = n_cus();
   if (ncu <= 0) return fail(DOL_EINVAL, "%s: no device", nm);
-  // measurement knobs: DOL_PM_VARIANT 1 = default-policy DMA loads, 4 = copy in
-  // this geometry (the structure's ceiling); DOL_PM_NSEG = stage-order segments
-  const int var = obj < 0 ? env_int("DOL_PM_VARIANT", 0) : 0;
   auto go = [&](auto kern) {
     const int lds = NB * SF * 4;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -470,32 +472,19 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kT1), lds, s, XT, ldx, x_rows, YT, ldy, n_rows, P,
                        xw, sr, qp_log2, spt, n_stages, nseg, rowptr, col, val, e, nw, wait_mode);
   };
-  using std::integral_constant;
-  if (obj >= 0) {  // small geometry only
-    auto ge = [&](auto oc, auto mc) {
-      constexpr int Oc = decltype(oc)::value, Mc = decltype(mc)::value;
-      if (dgeo == 1) go(csr_pm_kernel<kT1, 12288, 3, 1, 2, 2, false, Oc, Mc>);
-      else if (dgeo == 2) go(csr_pm_kernel<kT1, 20480, 2, 1, 2, 2, false, Oc, Mc>);
-      else go(csr_pm_kernel<kT1, 16384, 2, 1, 2, 2, false, Oc, Mc>);
-    };
-    using O0 = integral_constant<int, 0>;
-    using O1 = integral_constant<int, 1>;
-    using M0 = integral_constant<int, 0>;
-    using M1 = integral_constant<int, 1>;
-    using M2 = integral_constant<int, 2>;
-    if (obj == 0) { if (mode == 0) ge(O0{}, M0{}); else if (mode == 1) ge(O0{}, M1{}); else ge(O0{}, M2{}); }
-    else { if (mode == 0) ge(O1{}, M0{}); else if (mode == 1) ge(O1{}, M1{}); else ge(O1{}, M2{}); }
-    return check_launch(nm);
+  if (obj < 0) {
+    if (big) go(csr_pm_kernel<kT1, 8192, 5, 2>);
+    else go(csr_pm_kernel<kT1, 16384, 2, 1>);
+  } else if (mode == 2) {  // small geometry only
+    if (obj == 0) go(csr_pm_kernel<kT1, 20480, 2, 1, 0, 2>);
+    else go(csr_pm_kernel<kT1, 20480, 2, 1, 1, 2>);
+  } else if (obj == 0) {
+    if (mode == 0) go(csr_pm_kernel<kT1, 16384, 2, 1, 0, 0>);
+    else go(csr_pm_kernel<kT1, 16384, 2, 1, 0, 1>);
+  } else {
+    if (mode == 0) go(csr_pm_kernel<kT1, 16384, 2, 1, 1, 0>);
+    else go(csr_pm_kernel<kT1, 16384, 2, 1, 1, 1>);
   }
-  auto pick = [&](auto sfc, auto nbc, auto qc) {
-    constexpr int SFc = decltype(sfc)::value, NBc = decltype(nbc)::value, Qc = decltype(qc)::value;
-    if (var == 1) go(csr_pm_kernel<kT1, SFc, NBc, Qc, 0, 2>);
-    else if (var == 4) go(csr_pm_kernel<kT1, SFc, NBc, Qc, 2, 2, true>);
-    else go(csr_pm_kernel<kT1, SFc, NBc, Qc, 2, 2>);
-  };
-  if (big && big_nb == 5) pick(integral_constant<int, 8192>{}, integral_constant<int, 5>{}, integral_constant<int, 2>{});
-  else if (big) pick(integral_constant<int, 8192>{}, integral_constant<int, 4>{}, integral_constant<int, 2>{});
-  else pick(integral_constant<int, 16384>{}, integral_constant<int, 2>{}, integral_constant<int, 1>{});
   return check_launch(nm);
 }
 

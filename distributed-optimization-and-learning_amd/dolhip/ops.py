@@ -309,13 +309,18 @@ def csr_slab_pack(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x_
     return ent, hdr
 
 
-SLAB_VARIANTS = (1, 2, 3)  # 1: a loop per (row, chunk) segment (r03); 2: the wave's pairs as one pipelined stream (r06); 3: that stream hand-scheduled (asm)
+SLAB_VARIANTS = (2, 3)  # 2: the wave's pairs as one pipelined stream (r06); 3: that stream hand-scheduled (asm); 1 (a loop per row, r03) was retired
 
 
 def slab_variant(variant: int) -> int:
     """Kernel of mix_csr_slab for this process (dol_slab_set_variant; 0 =
-    the default).  Same bits for every variant.  Returns the previous setting."""
-    return int(_native.lib().dol_slab_set_variant(int(variant)))
+    the default, 3).  Same bits for every variant.  Returns the previous
+    setting; a variant the library refuses raises DolNativeError."""
+    L = _native.lib()
+    prev = int(L.dol_slab_set_variant(int(variant)))
+    if prev < 0:
+        raise DolNativeError(f"dol_slab_set_variant returned {prev}: {L.dol_last_error().decode(errors='replace')}")
+    return prev
 
 
 def slab_layout_ok(X: torch.Tensor, Y: torch.Tensor, P: int) -> bool:
@@ -592,7 +597,7 @@ def mix_dense_split3(W: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, P: Optio
     """Y = W X on the bf16 matrix cores at fp32 accuracy (dol_mix_dense_split3_f32:
     three-piece bf16 split of both operands, six piece products per term).
     fuse (None = when X's rows allow it, split3_x_flags, and M <=
-    SPLIT3_FUSE_MAX_M): X is split inside the GEMM (dense_split3_fx8_kernel:
+    SPLIT3_FUSE_MAX_M): X is split inside the GEMM (dense_split3_fxw_kernel:
     no split pass, no X workspace; same bits) instead of by a split pass.  Its
     GEMM runs ~6-8 % slower than the record-staged one, so it pays where the
     pass is a large share of the round, i.e. few output rows per X value:

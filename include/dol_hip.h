@@ -149,12 +149,12 @@ int dol_mix_csr_slab_f32(const float* X, int64_t ldx, int32_t x_rows, float* Y, 
  * worth it only when one W is mixed many times). */
 int dol_csr_slab_pack(const int32_t* rowptr, const int32_t* col, const float* val, int32_t n_rows,
                       int32_t x_rows, int32_t balance, int32_t* ent, int32_t* hdr, hipStream_t s);
-/* Kernel of dol_mix_csr_slab_f32 for this process: 0 = default (DOL_SLAB_KERNEL,
- * else 3), 1 = a loop per (row, chunk) segment (r03), 2 = each wave's pairs as
- * one software-pipelined stream (r06), 3 = that stream hand-scheduled in
- * assembly (r06; P >= 2^30 runs 2).  Same bits for every variant.  Returns the
- * previous setting, or DOL_EINVAL outside [0, 3].  No reference counterpart (a
- * launch choice). */
+/* Kernel of dol_mix_csr_slab_f32 for this process: 0 = default (3), 2 = each
+ * wave's pairs as one software-pipelined stream (r06), 3 = that stream
+ * hand-scheduled in assembly (r06; P >= 2^30 runs 2).  Same bits for every
+ * variant.  Returns the previous setting, or DOL_EINVAL outside [0, 3] and for
+ * 1 (a loop per (row, chunk) segment, r03: retired, the number is not reused).
+ * No reference counterpart (a launch choice). */
 int dol_slab_set_variant(int32_t variant);
 /*
  * Neighbors (DIST/simulators.py:91-97) of every row of a dense device W, on

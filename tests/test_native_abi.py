@@ -74,6 +74,20 @@ def test_pm_stage_order_setter():
     assert L.dol_ring_steps_set_variant(prev) == 2
 
 
+def test_slab_variant_setter():
+    L = _native.lib()
+    assert L.dol_slab_set_variant(1) == -1 and b"retired" in L.dol_last_error()  # the r03 row loop
+    assert L.dol_slab_set_variant(4) == -1 and b"outside" in L.dol_last_error()
+    assert L.dol_slab_set_variant(-1) == -1 and b"outside" in L.dol_last_error()
+    prev = L.dol_slab_set_variant(2)
+    assert L.dol_slab_set_variant(0) == 2
+    assert ops.slab_variant(prev) == 0
+    with pytest.raises(_native.DolNativeError, match="retired"):
+        ops.slab_variant(1)
+    assert ops.slab_variant(prev) == prev  # the refused call changed nothing
+    assert ops.SLAB_VARIANTS == (2, 3)
+
+
 def test_slab_entry_points_check_arguments():
     L = _native.lib()
     fake = 1 << 20  # never dereferenced

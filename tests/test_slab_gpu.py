@@ -201,7 +201,7 @@ def test_slab_pack_matches_host(n, p, balance, gpu):
     pairs = ent_d[: 2 * len(ent)].cpu().numpy().reshape(-1, 4)  # (w0, off0, w1, off1)
     got_e = np.stack([pairs[:, [1, 3]].reshape(-1), pairs[:, [0, 2]].reshape(-1)], axis=1)
     assert np.array_equal(got_e, ent)
-    # r06: pad entries right after the last block (the stream kernel reads up to two pairs past a run)
+    # r06: pad entries right after the last block (the stream kernel reads up to DOL_SLAB_STREAM_AHEAD = 3 pairs past a run)
     tail = ent_d[2 * len(ent): 2 * len(ent) + 16].cpu().numpy().reshape(-1, 2)
     assert np.array_equal(tail, np.tile([0, SLAB_ZERO_OFFSET], (8, 1)))
 

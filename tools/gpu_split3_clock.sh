@@ -1,7 +1,7 @@
 # Effective clock and MFMA busy of the split3 GEMMs (VERDICT r04 item 8's
 # stall breakdown): one kernel-trace pass and one PMC pass of
 # tools/split3_ab.py (1024 x 1024 x 101,770: the split-pass path and the fused
-# FX8 path).  Per kernel: median duration, GRBM_GUI_ACTIVE cycles per launch
+# FXW path).  Per kernel: median duration, GRBM_GUI_ACTIVE cycles per launch
 # (summed over the 8 XCDs) -> the effective clock, the SQ time split and
 # SQ_VALU_MFMA_BUSY_CYCLES per SIMD-cycle.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

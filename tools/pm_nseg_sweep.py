@@ -1,6 +1,6 @@
 """Parameter-major mix at 8192 x 2^20 (random 4-regular) under each stage order
-(DOL_PM_NSEG, read per launch) and its own-geometry copy (DOL_PM_VARIANT=4),
-beside the ring round on the same box; one JSON line.
+(DOL_PM_NSEG, read per launch), beside the ring round on the same box; one
+JSON line.
   python tools/pm_nseg_sweep.py [--reps 3]"""
 import argparse
 import json
@@ -43,10 +43,6 @@ def main():
     res = {"ring_ms": timed(lambda: ops.mix_ring(X, Y, wp, wn))}
     for ns in (1, 2, 4, 8, 16, 32, 64, 128, 256):
         res[f"pm_nseg{ns}_ms"] = timed(pm(ns))
-    os.environ["DOL_PM_VARIANT"] = "4"
-    for ns in (8, 16, 32, 64, 256):
-        res[f"pm_geometry_copy_nseg{ns}_ms"] = timed(pm(ns))
-    os.environ.pop("DOL_PM_VARIANT")
     res["pm_default_ms"] = timed(pm(0))
     res["pm_tuned_ms"] = timed(pm(None))
     res["pm_tuned"] = ops.pm_stage_order_choice(Y.view(P, N), X.view(P, N), N, P=P)

@@ -1,6 +1,6 @@
-"""A/B of the LDS-gather CSR mix's kernel variants (dol_slab_set_variant: 1 =
-a loop per (row, chunk) segment, r03; 2 = the wave's pairs as one pipelined
-stream, r06) on config 5's mix: 1024 agents x 101,770 (the 784-128-10 MLP),
+"""A/B of the LDS-gather CSR mix's kernel variants (dol_slab_set_variant: 2 =
+the wave's pairs as one pipelined stream, r06; 3 = that stream hand-scheduled)
+on config 5's mix: 1024 agents x 101,770 (the 784-128-10 MLP),
 Erdos-Renyi p = 0.1 W drawn on the device; plus 8192 x 1024.  Variants
 alternate in one process on the same buffers; every rep's output is compared
 bit for bit across variants.  One JSON line per (shape, variant, trial).

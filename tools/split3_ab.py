@@ -1,6 +1,5 @@
 """Dense ER mix on the bf16 matrix cores (split3): the split pass + record-staged
-GEMM vs the fused X split (dense_split3_fx8_kernel and dense_split3_fxw_kernel,
-r05; DOL_SPLIT3_FXW=1 selects the latter), alternating in one
+GEMM vs the fused X split (dense_split3_fxw_kernel, r05), alternating in one
 process at bench.dense_mix_round's shape (1024 agents x 101,770, ER p = 0.1,
 ld = row_stride(P)); one JSON line per (rep, path) with ms and the bf16 MFMA
 utilisation the bench reports (6 x 2 N^2 P flop / ms / 2516.6 TF)."""
@@ -29,9 +28,7 @@ def main():
         ops.mix_dense_split3(W, X, Y, P=P, work=work)
     torch.cuda.synchronize()
     for rep in range(4):
-        for path, fuse, env in (("split_pass", False, {}), ("fx8", True, {"DOL_SPLIT3_FXW": "0"}),
-                                ("fxw", True, {"DOL_SPLIT3_FXW": "1"})):
-            os.environ.update(env)  # read per call by dol_mix_dense_split3_f32
+        for path, fuse in (("split_pass", False), ("fxw", True)):
             for _ in range(20):
                 ops.mix_dense_split3(W, X, Y, P=P, work=work, fuse=fuse)
             torch.cuda.synchronize()

@@ -1,8 +1,7 @@
 """split3 at bench.dense_mix_round's shape (1024 x 1024 x 101,770, fused X
-split): the tail's quarter-tile kernel at 8 waves (4 x 2, default) vs 4 waves
-(2 x 2, DOL_SPLIT3_FX8_TAIL=4) vs no tail split (DOL_SPLIT3_CUS=0: the last
-partial wave runs as whole tiles), alternating in one process; outputs compared
-bit for bit.  One JSON line per (rep, path)."""
+split): the tail's quarter-tile kernel (4 x 2 waves) vs no tail split
+(DOL_SPLIT3_CUS=0: the last partial wave runs as whole tiles), alternating in
+one process; outputs compared bit for bit.  One JSON line per (rep, path)."""
 import json
 import os
 import sys
@@ -22,9 +21,7 @@ def main():
     W = G.erdos_renyi_stochastic(N, 0.1, gen)
     X = torch.empty(N, row_stride(P), device=dev).normal_(generator=gen)
     work = torch.empty(ops.dense_split3_workspace_bytes(N, N, P, 0), dtype=torch.uint8, device=dev)
-    paths = (("tail8", {"DOL_SPLIT3_FX8_TAIL": "8", "DOL_SPLIT3_CUS": ""}),
-             ("tail4", {"DOL_SPLIT3_FX8_TAIL": "4", "DOL_SPLIT3_CUS": ""}),
-             ("no_tail", {"DOL_SPLIT3_FX8_TAIL": "8", "DOL_SPLIT3_CUS": "0"}))
+    paths = (("tail8", {"DOL_SPLIT3_CUS": ""}), ("no_tail", {"DOL_SPLIT3_CUS": "0"}))
     outs = {name: torch.empty_like(X) for name, _ in paths}
     for _ in range(200):  # clocks up
         ops.mix_dense_split3(W, X, outs["tail8"], P=P, work=work)
