@@ -1,0 +1,766 @@
+// admm.hip — the primal/dual family on the agent-major bank: the fused prox /
+// ADMM gradient term + momentum SGD step, the dual update and its residuals,
+// the FedADMM least-squares client round (alone, and fused with the server's
+// ordered mean) and the ordered sum / mean.
+//
+// Dropped launch variant (the default's bits; code last present at 1a824fc):
+//   DOL_ADMM_ROUND_THREADS: admm_ls_round_mean_kernel strips forced to 1024 / 256 / 64 lanes; at 8192 x 2^17
+//     18.6 / 7.4 / 7.65 ms, and 5.15 for the two-kernel round (profiles/r06c_admm_narrow_ab.jsonl).
+#include <algorithm>
+
+#include "dol_launch.h"
+
+namespace {
+constexpr int kThreads = 256;            // 4 waves of 64
+
+// ----------------------------------------------------------------------------
+// Fused prox / ADMM gradient term + momentum SGD.
+// MODE: 0 = no momentum, 1 = momentum first step (buf = g'), 2 = momentum.
+// ----------------------------------------------------------------------------
+template <bool THETA, bool ALPHA, int MODE, bool WRITE_G, bool DUAL = false>
+__device__ __forceinline__ void prox_sgd_lane(float& w, float& bf, float& g, float th, float& al,
+                                              float rho, float neg_lr, float mom) {
+  float gg = g;
+  if constexpr (THETA) {
+    float t = rho * (w - th);
+    if constexpr (ALPHA) t = al + t;
+    gg = gg + t;
+  }
+  if constexpr (WRITE_G) g = gg;
+  float d = gg;
+  if constexpr (MODE == 1) { bf = gg; d = gg; }
+  if constexpr (MODE == 2) { bf = bf * mom + gg; d = bf; }
+  w = __builtin_fmaf(neg_lr, d, w);
+  if constexpr (DUAL) al = al + rho * (w - th);  // update_duals on the new w (DEC/clients.py:141-144)
+}
+
+template <typename V, bool THETA, bool ALPHA, int MODE, bool WRITE_G, bool DUAL = false>
+__global__ __launch_bounds__(kThreads) void prox_sgd_kernel(
+    float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ G,
+    int64_t ldg, const float* __restrict__ theta, float* __restrict__ A, int64_t lda,
+    float rho, float neg_lr, float mom, int64_t c_off, int64_t ncols_v, int64_t n_col_tiles) {
+  const int64_t blk = blockIdx.x;
+  const int64_t agent = blk / n_col_tiles;
+  const int64_t c = (blk % n_col_tiles) * kThreads + threadIdx.x;
+  if (c >= ncols_v) return;
+  V* wp = reinterpret_cast<V*>(W + agent * ldw + c_off) + c;
+  V* gp = reinterpret_cast<V*>(G + agent * ldg + c_off) + c;
+  // every per-agent row is read and written once: nontemporal both ways (r05:
+  // 100 x 1,663,370 0.83 vs 0.90 ms, 1024 x 2^20 4.67 vs 4.96 ms,
+  // profiles/r05zzr_prox_sgd_nt_ab.jsonl); theta is shared by all agents: cached
+  constexpr bool DOL_PROX_NT = true;
+  V w = ldv<V, DOL_PROX_NT>(wp), g = ldv<V, DOL_PROX_NT>(gp);
+  V bf{}, th{}, al{};
+  if constexpr (MODE == 2) bf = ldv<V, DOL_PROX_NT>(reinterpret_cast<V*>(B + agent * ldb + c_off) + c);
+  if constexpr (THETA) th = *(reinterpret_cast<const V*>(theta + c_off) + c);
+  if constexpr (ALPHA) al = ldv<V, DOL_PROX_NT>(reinterpret_cast<const V*>(A + agent * lda + c_off) + c);
+  if constexpr (Vec<V>::W == 1) {
+    prox_sgd_lane<THETA, ALPHA, MODE, WRITE_G, DUAL>(w, bf, g, th, al, rho, neg_lr, mom);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float wj = w[j], bj = bf[j], gj = g[j], aj = al[j];
+      prox_sgd_lane<THETA, ALPHA, MODE, WRITE_G, DUAL>(wj, bj, gj, th[j], aj, rho, neg_lr, mom);
+      w[j] = wj;
+      bf[j] = bj;
+      g[j] = gj;
+      al[j] = aj;
+    }
+  }
+  stv<V, DOL_PROX_NT>(wp, w);
+  if constexpr (WRITE_G) stv<V, DOL_PROX_NT>(gp, g);
+  if constexpr (MODE != 0) stv<V, DOL_PROX_NT>(reinterpret_cast<V*>(B + agent * ldb + c_off) + c, bf);
+  if constexpr (DUAL) stv<V, DOL_PROX_NT>(reinterpret_cast<V*>(A + agent * lda + c_off) + c, al);
+}
+
+// Gradient term alone: g += rho*(w - theta) (+ alpha), w untouched.
+template <typename V, bool ALPHA>
+__global__ __launch_bounds__(kThreads) void prox_grad_kernel(
+    float* __restrict__ G, int64_t ldg, const float* __restrict__ W, int64_t ldw,
+    const float* __restrict__ theta, const float* __restrict__ A, int64_t lda, float rho,
+    int64_t c_off, int64_t ncols_v, int64_t n_col_tiles) {
+  const int64_t blk = blockIdx.x;
+  const int64_t agent = blk / n_col_tiles;
+  const int64_t c = (blk % n_col_tiles) * kThreads + threadIdx.x;
+  if (c >= ncols_v) return;
+  V* gp = reinterpret_cast<V*>(G + agent * ldg + c_off) + c;
+  const V w = *(reinterpret_cast<const V*>(W + agent * ldw + c_off) + c);
+  const V th = *(reinterpret_cast<const V*>(theta + c_off) + c);
+  V t = rho * (w - th);
+  if constexpr (ALPHA) t = *(reinterpret_cast<const V*>(A + agent * lda + c_off) + c) + t;
+  *gp = *gp + t;
+}
+
+// ----------------------------------------------------------------------------
+// ADMM dual update alpha += rho*(w - theta), with optional per-agent
+// ||w-theta||^2 partials (fp64, fixed reduction tree -> deterministic).
+// One block = kThreads lanes x kDualIters V-columns of one agent.
+// ----------------------------------------------------------------------------
+constexpr int kDualIters = 4;
+
+__device__ __forceinline__ double block_sum_f64(double v, double* smem) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) smem[wid] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < kThreads / 64; ++i) s += smem[i];
+  }
+  return s;
+}
+
+__device__ __forceinline__ float dual_lane(float& a, float w, float th, float rho, double& r) {
+  const float d = w - th;
+  a = a + rho * d;
+  r += double(d) * double(d);
+  return d;
+}
+
+// VEC: columns [0, n4) as f4, then the (< 4) tail columns by the first
+// lanes of the agent's last chunk; !VEC: all P columns scalar.
+template <bool VEC, bool RESID>
+__global__ __launch_bounds__(kThreads) void admm_dual_kernel(
+    float* __restrict__ A, int64_t lda, const float* __restrict__ W, int64_t ldw,
+    const float* __restrict__ theta, float rho, int64_t P, int64_t n_chunks,
+    double* __restrict__ partial) {
+  __shared__ double smem[kThreads / 64];
+  const int64_t blk = blockIdx.x;
+  const int64_t agent = blk / n_chunks;
+  const int64_t chunk = blk % n_chunks;
+  float* arow = A + agent * lda;
+  const float* wrow = W + agent * ldw;
+  double r = 0.0;
+  if constexpr (VEC) {
+    const int64_t n4 = P / 4;
+#pragma unroll
+    for (int it = 0; it < kDualIters; ++it) {
+      const int64_t c = (chunk * kDualIters + it) * kThreads + threadIdx.x;
+      if (c < n4) {
+        // rows read / written once: nontemporal (r05: 100 x 1,663,370 0.378 vs
+        // 0.395 ms, 1024 x 2^20 2.16 vs 2.37 ms, profiles/r05zzs_admm_dual_nt_ab.jsonl)
+        constexpr bool DOL_DUAL_NT = true;
+        f4* ap = reinterpret_cast<f4*>(arow) + c;
+        const f4 w = ldv<f4, DOL_DUAL_NT>(reinterpret_cast<const f4*>(wrow) + c);
+        const f4 th = reinterpret_cast<const f4*>(theta)[c];
+        f4 a = ldv<f4, DOL_DUAL_NT>(ap);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float aj = a[j];
+          dual_lane(aj, w[j], th[j], rho, r);
+          a[j] = aj;
+        }
+        stv<f4, DOL_DUAL_NT>(ap, a);
+      }
+    }
+    const int64_t tail = P - 4 * n4;
+    if (chunk == n_chunks - 1 && threadIdx.x < tail) {
+      const int64_t c = 4 * n4 + threadIdx.x;
+      float a = arow[c];
+      dual_lane(a, wrow[c], theta[c], rho, r);
+      arow[c] = a;
+    }
+  } else {
+#pragma unroll
+    for (int it = 0; it < kDualIters; ++it) {
+      const int64_t c = (chunk * kDualIters + it) * kThreads + threadIdx.x;
+      if (c < P) {
+        float a = arow[c];
+        dual_lane(a, wrow[c], theta[c], rho, r);
+        arow[c] = a;
+      }
+    }
+  }
+  if constexpr (RESID) {
+    const double s = block_sum_f64(r, smem);
+    if (threadIdx.x == 0) partial[agent * n_chunks + chunk] = s;
+  }
+}
+
+// partial layout: [n_agents][n_chunks_total]; one block per agent, fixed order.
+__global__ __launch_bounds__(kThreads) void resid_reduce_kernel(const double* __restrict__ partial,
+                                                                int64_t n_chunks,
+                                                                double* __restrict__ out) {
+  __shared__ double smem[kThreads / 64];
+  const int64_t agent = blockIdx.x;
+  double v = 0.0;
+  for (int64_t i = threadIdx.x; i < n_chunks; i += kThreads) v += partial[agent * n_chunks + i];
+  const double s = block_sum_f64(v, smem);
+  if (threadIdx.x == 0) out[agent] = s;
+}
+
+// ----------------------------------------------------------------------------
+// One FedADMM client round on the separable least-squares objective
+// f_k(w) = 1/2 ||w - t_k||^2 (BASELINE config 4's primal/dual side), fused
+// per sampled agent k (row a = agents[k]) — the reference's
+// FedAdmm_Client.update_weights (DEC/clients.py:36-53) with the CNN gradient
+// replaced by the exact least-squares one:
+//   w = theta                                   (load_state_dict(theta), :37)
+//   local_steps times:  g = fl(w - t)
+//     g' = fl(g + fl(alpha + fl(rho * fl(w - theta))))        (:132-135)
+//     SGD(lr, momentum).step(): buf = first ? g' : fl(fl(buf*mu) + g'); w = fma(-lr, buf, w)
+//   alpha = fl(alpha + fl(rho * fl(w - theta)))  (update_duals, :141-144, pre-round theta)
+// Streams t, alpha (, buf) in and w, alpha (, buf) out once; w is never read.
+// RESID: fp64 per-block partials of ||w - theta||^2 and ||alpha||^2 (fixed
+// reduction tree, deterministic), as admm_dual_kernel.
+// ----------------------------------------------------------------------------
+template <bool MOM>
+__device__ __forceinline__ void admm_ls_lane(float& w, float& b, float& a, float t, float th, float rho,
+                                             float neg_lr, float mom, int steps, bool first, double& rw,
+                                             double& ra) {
+  w = th;
+  for (int k = 0; k < steps; ++k) {
+    const float g = w - t;
+    const float gg = g + (a + rho * (w - th));
+    float d = gg;
+    if constexpr (MOM) {
+      b = (first && k == 0) ? gg : b * mom + gg;
+      d = b;
+    }
+    w = __builtin_fmaf(neg_lr, d, w);
+  }
+  const float dl = w - th;
+  a = a + rho * dl;
+  // the product of two floats is exact in double, so fma == the reference's
+  // separately rounded rw + d*d, one instruction fewer
+  rw = __builtin_fma(double(dl), double(dl), rw);
+  ra = __builtin_fma(double(a), double(a), ra);
+}
+
+// The same lane on two columns at once: packed fp32 (v_pk_add / v_pk_mul /
+// v_pk_fma_f32 on gfx950, each an IEEE operation per half), same rounding per
+// element as admm_ls_lane.  At 10 local steps the round runs ~70 fp32 ops per
+// element: unpacked that is ~60 % of the HBM time in VALU issue.
+typedef float f2 __attribute__((ext_vector_type(2)));
+template <bool MOM>
+__device__ __forceinline__ void admm_ls_lane2(f2& w, f2& b, f2& a, f2 t, f2 th, float rho, float neg_lr, float mom,
+                                              int steps, bool first, double& rw, double& ra) {
+  const f2 rho2 = {rho, rho}, nlr2 = {neg_lr, neg_lr}, mom2 = {mom, mom};
+  w = th;
+  for (int k = 0; k < steps; ++k) {
+    const f2 g = w - t;
+    const f2 gg = g + (a + rho2 * (w - th));
+    f2 d = gg;
+    if constexpr (MOM) {
+      b = (first && k == 0) ? gg : b * mom2 + gg;
+      d = b;
+    }
+    w = __builtin_elementwise_fma(nlr2, d, w);
+  }
+  const f2 dl = w - th;
+  a = a + rho2 * dl;
+  rw = __builtin_fma(double(dl.x), double(dl.x), rw);
+  rw = __builtin_fma(double(dl.y), double(dl.y), rw);
+  ra = __builtin_fma(double(a.x), double(a.x), ra);
+  ra = __builtin_fma(double(a.y), double(a.y), ra);
+}
+// f4 = two packed halves
+template <bool MOM>
+__device__ __forceinline__ void admm_ls_lane4(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
+                                              int steps, bool first, double& rw, double& ra) {
+  f2 w0, w1, b0 = b.xy, b1 = b.zw, a0 = a.xy, a1 = a.zw;
+  admm_ls_lane2<MOM>(w0, b0, a0, t.xy, th.xy, rho, neg_lr, mom, steps, first, rw, ra);
+  admm_ls_lane2<MOM>(w1, b1, a1, t.zw, th.zw, rho, neg_lr, mom, steps, first, rw, ra);
+  w = f4{w0.x, w0.y, w1.x, w1.y};
+  b = f4{b0.x, b0.y, b1.x, b1.y};
+  a = f4{a0.x, a0.y, a1.x, a1.y};
+}
+
+template <bool VEC, bool MOM, bool RESID>
+__global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
+    float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ A, int64_t lda,
+    const float* __restrict__ T, int64_t ldt, const float* __restrict__ theta, const int32_t* __restrict__ agents,
+    const int32_t* __restrict__ first, int64_t P, float rho, float neg_lr, float mom, int steps, int64_t n_chunks,
+    double* __restrict__ partial) {
+  __shared__ double smem[kThreads / 64];
+  // agent-major blocks (consecutive blocks stream one row; a column-major order
+  // put 2048 rows 4 MiB apart in flight at once and ran 1-2 % slower).  The
+  // rows stream with nontemporal loads / stores so theta (4 MiB at 2^20, one
+  // XCD's L2) stays resident for the next row instead of being evicted by them
+  const int64_t blk = blockIdx.x;
+  const int64_t k = blk / n_chunks;
+  const int64_t chunk = blk % n_chunks;
+  const int64_t a_row = agents ? agents[k] : k;
+  const bool fst = first ? first[k] != 0 : false;
+  float* wr = W + a_row * ldw;
+  float* br = B + a_row * ldb;
+  float* ar = A + a_row * lda;
+  const float* tr = T + a_row * ldt;
+  double rw = 0.0, ra = 0.0;
+  auto one = [&](int64_t c) {
+    float w, b = MOM ? br[c] : 0.0f, a = ar[c];
+    admm_ls_lane<MOM>(w, b, a, tr[c], theta[c], rho, neg_lr, mom, steps, fst, rw, ra);
+    wr[c] = w;
+    ar[c] = a;
+    if constexpr (MOM) br[c] = b;
+  };
+  if constexpr (VEC) {
+    const int64_t n4 = P / 4;
+#pragma unroll
+    for (int it = 0; it < kDualIters; ++it) {
+      const int64_t c = (chunk * kDualIters + it) * kThreads + threadIdx.x;
+      if (c < n4) {
+        const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(tr) + c);
+        const f4 th = reinterpret_cast<const f4*>(theta)[c];
+        f4 a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ar) + c);
+        f4 b = MOM ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(br) + c) : f4{0.f, 0.f, 0.f, 0.f};
+        f4 w;
+        admm_ls_lane4<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, fst, rw, ra);
+        __builtin_nontemporal_store(w, reinterpret_cast<f4*>(wr) + c);
+        __builtin_nontemporal_store(a, reinterpret_cast<f4*>(ar) + c);
+        if constexpr (MOM) __builtin_nontemporal_store(b, reinterpret_cast<f4*>(br) + c);
+      }
+    }
+    const int64_t tail = P - 4 * n4;
+    if (chunk == n_chunks - 1 && threadIdx.x < tail) one(4 * n4 + threadIdx.x);
+  } else {
+#pragma unroll
+    for (int it = 0; it < kDualIters; ++it) {
+      const int64_t c = (chunk * kDualIters + it) * kThreads + threadIdx.x;
+      if (c < P) one(c);
+    }
+  }
+  if constexpr (RESID) {
+    const double sw = block_sum_f64(rw, smem);
+    __syncthreads();
+    const double sa = block_sum_f64(ra, smem);
+    if (threadIdx.x == 0) {
+      partial[k * n_chunks + chunk] = sw;
+      partial[(gridDim.x / n_chunks + k) * n_chunks + chunk] = sa;
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------
+// Ordered sum / mean over gathered rows: acc = w[o0]; acc += w[o1]; ...
+// Column-parallel; the row loop is unrolled so 8 row loads are in flight.
+// ----------------------------------------------------------------------------
+template <typename V>
+__global__ __launch_bounds__(kThreads) void ordered_sum_kernel(
+    const float* __restrict__ W, int64_t ldw, const int32_t* __restrict__ order, int m,
+    int64_t c_off, int64_t ncols_v, const float* __restrict__ acc_in, float* __restrict__ out,
+    float scale, int do_div) {
+  const int64_t c = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (c >= ncols_v) return;
+  const V* wb = reinterpret_cast<const V*>(W + c_off) + c;
+  const int64_t ldv = ldw / Vec<V>::W;
+  V acc;
+  int k;
+  if (acc_in) {
+    acc = *(reinterpret_cast<const V*>(acc_in + c_off) + c);
+    k = 0;
+  } else {
+    acc = wb[int64_t(order[0]) * ldv];
+    k = 1;
+  }
+  // the rows are read once: nontemporal loads (8192 x 2^20: 5.07-5.14 ms =
+  // 6.77 TB/s vs 5.66-5.74 ms plain; 16 rows in flight instead of 8: no change;
+  // profiles/r05zze_ordered_sum_ab.jsonl)
+  for (; k + 8 <= m; k += 8) {
+    V x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) x[u] = __builtin_nontemporal_load(wb + int64_t(order[k + u]) * ldv);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = vadd(acc, x[u]);
+  }
+  for (; k < m; ++k) acc = vadd(acc, __builtin_nontemporal_load(wb + int64_t(order[k]) * ldv));
+  if (do_div) acc = vdiv(acc, scale);
+  *(reinterpret_cast<V*>(out + c_off) + c) = acc;
+}
+
+// ----------------------------------------------------------------------------
+// The FedADMM client round fused with the server's ordered mean (one round of
+// DEC/servers.py:50-81 on least squares: every sampled client's
+// update_weights, DEC/clients.py:36-53, then average_weights, :42-48).
+// Column-strip major: each lane owns one V-column and walks the m sampled
+// agents in the given order, running admm_ls_lane on (agent, column) and
+// chaining acc = w(first) ; acc = fl(acc + w) — the ordered_sum_kernel's
+// association, so theta_next is the same bits as admm_ls_round_kernel +
+// ordered_sum_kernel — while the w rows are still in registers: the separate
+// mean read every sampled row back from HBM (34 GB at 8192 x 2^20, 15 % of the
+// round's bytes).  theta is read once per lane, not once per (agent, column).
+// The next agent group's t / alpha / buf loads are issued before the current
+// group's steps (kRoundPF agents in flight per lane).
+// RESID: fp64 per-lane sums over the agents of (w - theta)^2 and alpha^2, a
+// fixed block tree, one partial per block; resid_reduce_kernel folds the
+// blocks in a fixed order (the round's totals, not per agent).
+// ----------------------------------------------------------------------------
+constexpr int kRoundPF = 3;
+
+template <bool MOM>
+__device__ __forceinline__ void admm_ls_lane_v(float& w, float& b, float& a, float t, float th, float rho, float neg_lr,
+                                               float mom, int steps, bool first, double& rw, double& ra) {
+  admm_ls_lane<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
+}
+// packed (measured at 8192 x 2^20, 10 steps: 34.6-35.1 ms vs 36.0-36.5 with
+// the per-element scalar form, profiles/r05zw_admm_round_ab.jsonl)
+template <bool MOM>
+__device__ __forceinline__ void admm_ls_lane_v(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
+                                               int steps, bool first, double& rw, double& ra) {
+  admm_ls_lane4<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
+}
+__device__ __forceinline__ float ldnt(const float* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ f4 ldnt(const f4* p) { return __builtin_nontemporal_load(p); }
+// nontemporal buffer store of lane value v at byte offset voff of the row at
+// base (row-uniform resource); voff = kOOB drops it (still issued and counted)
+__device__ __forceinline__ void st_row(float v, float* base, int64_t nbytes, uint32_t voff) {
+  const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(nbytes), 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, voff, 0, 2);
+}
+__device__ __forceinline__ void st_row(f4 v, float* base, int64_t nbytes, uint32_t voff) {
+  const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(nbytes), 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), rs, voff, 0, 2);
+}
+
+template <int NT>
+__device__ __forceinline__ double block_sum_f64_nt(double v, double* smem) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) smem[wid] = v;
+  __syncthreads();
+  double s = 0.0;
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < NT / 64; ++i) s += smem[i];
+  }
+  return s;
+}
+
+template <typename V, bool MOM, bool RESID, int NT, int PF = kRoundPF>
+__global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
+    float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ A, int64_t lda,
+    const float* __restrict__ T, int64_t ldt, const float* __restrict__ theta, const int32_t* __restrict__ agents,
+    const int32_t* __restrict__ first, int m, int64_t c_off, int64_t ncols_v, float rho, float neg_lr, float mom,
+    int steps, float* __restrict__ out, float scale, int do_div, double* __restrict__ partial, int64_t part_off,
+    int64_t part_stride) {
+  __shared__ double smem[NT / 64];
+  const int64_t c = int64_t(blockIdx.x) * NT + threadIdx.x;
+  const bool live = c < ncols_v;
+  if (!RESID && !live) return;
+  // dead lanes (RESID only) read the last real column and compute on it; their
+  // stores are buffer stores pointed out of range (dropped, still counted, so
+  // every lane issues the same memory ops and the loop's vmcnt waits stay
+  // exact) and their residual terms are dropped
+  const int64_t cc = live ? c : ncols_v - 1;
+  const uint32_t voff = live ? uint32_t(c) * uint32_t(sizeof(V)) : kOOB;
+  auto st = [&](V v, float* base, int64_t ld, int64_t row) {
+    st_row(v, base + row * ld + c_off, std::min<int64_t>((ld - c_off) * 4, 0x7ffffff0), voff);
+  };
+  auto cptr = [&](const float* base, int64_t ld, int64_t row) {
+    return reinterpret_cast<const V*>(base + row * ld + c_off) + cc;
+  };
+  auto row_of = [&](int k) -> int64_t {  // agent k's row; k past m: the last agent's (a harmless re-read)
+    k = min(k, m - 1);
+    return agents ? agents[k] : k;
+  };
+  const V th = *cptr(theta, 0, 0);
+  V acc = vzero(th);
+  double rw = 0.0, ra = 0.0;
+  struct Grp {
+    V t[PF], a[PF], b[PF];
+    int64_t row[PF];
+  };
+  auto load = [&](Grp& g, int k0) {  // agents k0 .. k0 + PF - 1, unconditionally (rows clamped)
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      g.row[u] = row_of(k0 + u);
+      g.t[u] = ldnt(cptr(T, ldt, g.row[u]));
+      g.a[u] = ldnt(cptr(A, lda, g.row[u]));
+      if constexpr (MOM) g.b[u] = ldnt(cptr(B, ldb, g.row[u]));
+    }
+  };
+  auto run = [&](Grp& g, int u, int k) {  // agent k = group slot u: its steps, stores, and the chain
+    const bool fst = first ? first[k] != 0 : false;
+    V w, bu = MOM ? g.b[u] : vzero(th), au = g.a[u];
+    double rwu = 0.0, rau = 0.0;
+    admm_ls_lane_v<MOM>(w, bu, au, g.t[u], th, rho, neg_lr, mom, steps, fst, rwu, rau);
+    st(w, W, ldw, g.row[u]);
+    st(au, A, lda, g.row[u]);
+    if constexpr (MOM) st(bu, B, ldb, g.row[u]);
+    rw += live ? rwu : 0.0;
+    ra += live ? rau : 0.0;
+    acc = k == 0 ? w : vadd(acc, w);
+  };
+  const int ng = (m + PF - 1) / PF;  // groups; all but the last are full
+  Grp nxt, cur;
+  load(nxt, 0);
+  for (int gi = 0; gi + 1 < ng; ++gi) {  // straight-line body: the same memory ops every trip
+    cur = nxt;
+    load(nxt, (gi + 1) * PF);      // the next group's loads fly during this group's steps
+#pragma unroll
+    for (int u = 0; u < PF; ++u) run(cur, u, gi * PF + u);
+  }
+#pragma unroll
+  for (int u = 0; u < PF; ++u) {   // the last group (maybe partial)
+    const int k = (ng - 1) * PF + u;
+    if (k < m) run(nxt, u, k);
+  }
+  if (live) {
+    if (do_div) acc = vdiv(acc, scale);
+    *(reinterpret_cast<V*>(out + c_off) + c) = acc;
+  }
+  if constexpr (RESID) {
+    const double sw = block_sum_f64_nt<NT>(rw, smem);
+    __syncthreads();
+    const double sa = block_sum_f64_nt<NT>(ra, smem);
+    if (threadIdx.x == 0) {
+      partial[part_off + blockIdx.x] = sw;
+      partial[part_stride + part_off + blockIdx.x] = sa;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dol_prox_admm_sgd_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* g, int64_t ldg,
+                          const float* theta, const float* alpha, int64_t lda, float rho, float lr,
+                          float momentum, int first_step, int write_grad, int32_t n_agents,
+                          int64_t P, hipStream_t s) {
+  DOL_DIMS_OK("dol_prox_admm_sgd_f32", ldw, ldb, ldg, lda, P);
+  DOL_CHECKED(check_size("dol_prox_admm_sgd_f32", n_agents < 0 || P < 0, n_agents == 0 || P == 0));
+  if (!w || !g) return fail(DOL_EINVAL, "dol_prox_admm_sgd_f32: null w or g");
+  if (alpha && !theta) return fail(DOL_EINVAL, "dol_prox_admm_sgd_f32: alpha without theta");
+  const int mode = momentum_mode(momentum, first_step);
+  if (mode != 0 && !buf) return fail(DOL_EINVAL, "dol_prox_admm_sgd_f32: momentum needs buf");
+  if (ldw < P || ldg < P || (mode != 0 && ldb < P) || (alpha && lda < P))
+    return fail(DOL_EINVAL, "dol_prox_admm_sgd_f32: ld < P");
+  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(g, ldg) && (mode == 0 || row_vec_ok(buf, ldb)) &&
+                      row_vec_ok(theta, 0) && row_vec_ok(alpha, alpha ? lda : 0);
+  const ColSplit cs = split_cols(P, vec_ok);
+  if (mul_sat(cdiv(cs.n4 + cs.tail, kThreads), n_agents) > kMaxBlocks)
+    return fail(DOL_EINVAL, "dol_prox_admm_sgd_f32: problem too large for one launch");
+  const int terms = (theta != nullptr) + (alpha != nullptr);  // 0 plain SGD, 1 prox (theta), 2 ADMM (theta and alpha)
+  auto launch = [&](auto vtag, int64_t c_off, int64_t nc) {
+    const int64_t nct = cdiv(nc, kThreads);
+    dispatch([&](auto tc, auto mc, auto wg) {
+      constexpr int T = decltype(tc)::value;
+      // alpha is only read on this path (the kernel's pointer is non-const for the fused-dual variant)
+      hipLaunchKernelGGL((prox_sgd_kernel<decltype(vtag), T >= 1, T == 2, decltype(mc)::value, decltype(wg)::value>),
+                         dim3(static_cast<unsigned>(nct * n_agents)), dim3(kThreads), 0, s, w, ldw, buf, ldb, g, ldg,
+                         theta, const_cast<float*>(alpha), lda, rho, -lr, momentum, c_off, nc, nct);
+    }, Ints<0, 1, 2>{terms}, Ints<0, 1, 2>{mode}, Bool{write_grad != 0});
+  };
+  if (cs.n4 > 0) launch(f4{}, 0, cs.n4);
+  if (cs.tail > 0) launch(float{}, cs.n4 * 4, cs.tail);
+  return check_launch("dol_prox_admm_sgd_f32");
+}
+
+int dol_admm_step_dual_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* g, int64_t ldg,
+                           const float* theta, float* alpha, int64_t lda, float rho, float lr,
+                           float momentum, int first_step, int write_grad, int32_t n_agents, int64_t P,
+                           hipStream_t s) {
+  DOL_DIMS_OK("dol_admm_step_dual_f32", ldw, ldb, ldg, lda, P);
+  DOL_CHECKED(check_rows("dol_admm_step_dual_f32", n_agents < 0 || P < 0, n_agents == 0 || P == 0,
+                         !w || !g || !theta || !alpha, false, false));
+  const int mode = momentum_mode(momentum, first_step);
+  if (mode != 0 && !buf) return fail(DOL_EINVAL, "dol_admm_step_dual_f32: momentum needs buf");
+  if (ldw < P || ldg < P || lda < P || (mode != 0 && ldb < P)) return fail(DOL_EINVAL, "dol_admm_step_dual_f32: ld < P");
+  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(g, ldg) && (mode == 0 || row_vec_ok(buf, ldb)) &&
+                      row_vec_ok(theta, 0) && row_vec_ok(alpha, lda);
+  const ColSplit cs = split_cols(P, vec_ok);
+  if (mul_sat(cdiv(cs.n4 + cs.tail, kThreads), n_agents) > kMaxBlocks) return fail(DOL_EINVAL, "dol_admm_step_dual_f32: too large");
+  auto launch = [&](auto vtag, int64_t c_off, int64_t nc) {
+    const int64_t nct = cdiv(nc, kThreads);
+    dispatch([&](auto mc, auto wg) {
+      hipLaunchKernelGGL((prox_sgd_kernel<decltype(vtag), true, true, decltype(mc)::value, decltype(wg)::value, true>),
+                         dim3(static_cast<unsigned>(nct * n_agents)), dim3(kThreads), 0, s, w, ldw, buf, ldb, g, ldg,
+                         theta, alpha, lda, rho, -lr, momentum, c_off, nc, nct);
+    }, Ints<0, 1, 2>{mode}, Bool{write_grad != 0});
+  };
+  if (cs.n4 > 0) launch(f4{}, 0, cs.n4);
+  if (cs.tail > 0) launch(float{}, cs.n4 * 4, cs.tail);
+  return check_launch("dol_admm_step_dual_f32");
+}
+
+int dol_prox_grad_f32(float* g, int64_t ldg, const float* w, int64_t ldw, const float* theta,
+                      const float* alpha, int64_t lda, float rho, int32_t n_agents, int64_t P,
+                      hipStream_t s) {
+  DOL_DIMS_OK("dol_prox_grad_f32", ldg, ldw, lda, P);
+  DOL_CHECKED(check_rows("dol_prox_grad_f32", n_agents < 0 || P < 0, n_agents == 0 || P == 0, !g || !w || !theta,
+                         ldg < P || ldw < P || (alpha && lda < P), false));
+  const bool vec_ok = row_vec_ok(g, ldg) && row_vec_ok(w, ldw) && row_vec_ok(theta, 0) &&
+                      row_vec_ok(alpha, alpha ? lda : 0);
+  const ColSplit cs = split_cols(P, vec_ok);
+  auto launch = [&](auto vtag, int64_t c_off, int64_t nc) {
+    using V = decltype(vtag);
+    const int64_t nct = cdiv(nc, kThreads);
+    const dim3 grid(static_cast<unsigned>(nct * n_agents));
+    dispatch([&](auto al) {
+      hipLaunchKernelGGL((prox_grad_kernel<V, decltype(al)::value>), grid, dim3(kThreads), 0, s, g, ldg, w, ldw, theta,
+                         alpha, lda, rho, c_off, nc, nct);
+    }, Bool{alpha != nullptr});
+  };
+  if (mul_sat(cdiv(cs.n4 + cs.tail, kThreads), n_agents) > kMaxBlocks) return fail(DOL_EINVAL, "dol_prox_grad_f32: too large");
+  if (cs.n4 > 0) launch(f4{}, 0, cs.n4);
+  if (cs.tail > 0) launch(float{}, cs.n4 * 4, cs.tail);
+  return check_launch("dol_prox_grad_f32");
+}
+
+int64_t dol_admm_dual_workspace_bytes(int32_t n_agents, int64_t P) {
+  if (n_agents <= 0 || P <= 0 || P > dol::kMaxDim) return 0;
+  // the scalar path has the most chunks: cdiv(P, kThreads*kDualIters)
+  return int64_t(n_agents) * cdiv(P, int64_t(kThreads) * kDualIters) * int64_t(sizeof(double));
+}
+
+int dol_admm_dual_f32(float* alpha, int64_t lda, const float* w, int64_t ldw, const float* theta,
+                      float rho, int32_t n_agents, int64_t P, double* resid_sq, void* work,
+                      hipStream_t s) {
+  DOL_DIMS_OK("dol_admm_dual_f32", lda, ldw, P);
+  DOL_CHECKED(check_size("dol_admm_dual_f32", n_agents < 0 || P < 0, n_agents == 0));
+  if (P > 0 && (!alpha || !w || !theta)) return fail(DOL_EINVAL, "dol_admm_dual_f32: null pointer");
+  if (resid_sq && !work && P > 0) return fail(DOL_EINVAL, "dol_admm_dual_f32: resid_sq needs a workspace");
+  if (lda < P || ldw < P) return fail(DOL_EINVAL, "dol_admm_dual_f32: ld < P");
+  if (P == 0) {
+    if (resid_sq) (void)hipMemsetAsync(resid_sq, 0, sizeof(double) * n_agents, s);
+    return check_launch("dol_admm_dual_f32");
+  }
+  const bool vec = row_vec_ok(alpha, lda) && row_vec_ok(w, ldw) && row_vec_ok(theta, 0);
+  const int64_t per_block = int64_t(kThreads) * kDualIters;
+  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
+  if (mul_sat(chunks, n_agents) > kMaxBlocks) return fail(DOL_EINVAL, "dol_admm_dual_f32: problem too large");
+  double* partial = static_cast<double*>(work);
+  const dim3 grid(static_cast<unsigned>(chunks * n_agents));
+  dispatch([&](auto vc, auto rc) {
+    hipLaunchKernelGGL((admm_dual_kernel<decltype(vc)::value, decltype(rc)::value>), grid, dim3(kThreads), 0, s, alpha,
+                       lda, w, ldw, theta, rho, P, chunks, partial);
+  }, Bool{vec}, Bool{resid_sq != nullptr});
+  if (resid_sq) hipLaunchKernelGGL(resid_reduce_kernel, dim3(n_agents), dim3(kThreads), 0, s, partial, chunks, resid_sq);
+  return check_launch("dol_admm_dual_f32");
+}
+
+int64_t dol_admm_ls_round_workspace_bytes(int32_t m, int64_t P) {
+  if (m <= 0 || P <= 0 || P > dol::kMaxDim) return 0;
+  return 2 * dol_admm_dual_workspace_bytes(m, P);  // ||w - theta||^2 and ||alpha||^2 partials
+}
+
+int dol_admm_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                          const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                          const int32_t* first, int32_t m, int64_t P, float rho, float lr, float momentum,
+                          int32_t local_steps, double* resid_sq, double* alpha_sq, void* work, hipStream_t s) {
+  DOL_DIMS_OK("dol_admm_ls_round_f32", ldw, ldb, lda, ldt, P);
+  const char* nm = "dol_admm_ls_round_f32";
+  const bool mom = momentum != 0.0f;
+  DOL_CHECKED(check_rows(nm, m < 0 || P < 0 || local_steps < 0, m == 0,
+                         P > 0 && (!w || !alpha || !target || !theta || (mom && !buf)), false, false));
+  if ((resid_sq == nullptr) != (alpha_sq == nullptr)) return fail(DOL_EINVAL, "%s: pass both residual outputs or neither", nm);
+  if (resid_sq && !work && P > 0) return fail(DOL_EINVAL, "%s: residuals need a workspace", nm);
+  if (ldw < P || lda < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P == 0) {
+    if (resid_sq) {
+      (void)hipMemsetAsync(resid_sq, 0, sizeof(double) * m, s);
+      (void)hipMemsetAsync(alpha_sq, 0, sizeof(double) * m, s);
+    }
+    return check_launch(nm);
+  }
+  const bool vec = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
+                   (!mom || row_vec_ok(buf, ldb));
+  const int64_t per_block = int64_t(kThreads) * kDualIters;
+  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
+  if (mul_sat(chunks, m) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large", nm);
+  double* partial = static_cast<double*>(work);
+  const dim3 grid(static_cast<unsigned>(chunks * m));
+  dispatch([&](auto vc, auto mc, auto rc) {
+    hipLaunchKernelGGL((admm_ls_round_kernel<decltype(vc)::value, decltype(mc)::value, decltype(rc)::value>), grid,
+                       dim3(kThreads), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents, first, P, rho,
+                       -lr, momentum, local_steps, chunks, partial);
+  }, Bool{vec}, Bool{mom}, Bool{resid_sq != nullptr});
+  if (resid_sq) {
+    hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial, chunks, resid_sq);
+    hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial + int64_t(m) * chunks, chunks,
+                       alpha_sq);
+  }
+  return check_launch(nm);
+}
+
+int64_t dol_admm_ls_round_mean_workspace_bytes(int64_t P) {
+  if (P <= 0 || P > dol::kMaxDim) return 0;
+  return 2 * (cdiv(P, 64) + 2) * int64_t(sizeof(double));  // [2][blocks]: (w - theta)^2, alpha^2 (64-lane blocks)
+}
+
+int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                               const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                               const int32_t* first, int32_t m, int64_t P, float rho, float lr, float momentum,
+                               int32_t local_steps, float* theta_out, float scale, double* resid_total, void* work,
+                               hipStream_t s) {
+  DOL_DIMS_OK("dol_admm_ls_round_mean_f32", ldw, ldb, lda, ldt, P);
+  const char* nm = "dol_admm_ls_round_mean_f32";
+  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the average indexes w[0])", nm);
+  if (P < 0 || local_steps < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (!(scale > 0.0f)) return fail(DOL_EINVAL, "%s: scale must be > 0", nm);
+  const bool mom = momentum != 0.0f;
+  if (P > 0 && (!w || !alpha || !target || !theta || !theta_out || (mom && !buf)))
+    return fail(DOL_EINVAL, "%s: null pointer", nm);
+  if (theta_out == w || theta_out == alpha || theta_out == target || (mom && theta_out == buf))
+    return fail(DOL_EINVAL, "%s: theta_out aliases the rows", nm);
+  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
+  if (ldw < P || lda < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  if (P == 0) {
+    if (resid_total) (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
+    return check_launch(nm);
+  }
+  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) &&
+                      row_vec_ok(theta, 0) && row_vec_ok(theta_out, 0) && (!mom || row_vec_ok(buf, ldb));
+  const ColSplit cs = split_cols(P, vec_ok);
+  // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
+  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
+  // lanes per CU) take 256-lane strips: the strips are the only parallelism
+  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
+  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
+  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
+  // for the two-kernel round (row-major client round + ordered sum), which
+  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
+  const int n_cu = n_cus() > 0 ? n_cus() : 256;
+  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
+  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
+  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
+  const int64_t nb = nb4 + nbt;
+  double* partial = static_cast<double*>(work);
+  const int do_div = scale != 1.0f;
+  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
+    dispatch([&](auto mc, auto rc, auto ntc) {
+      hipLaunchKernelGGL((admm_ls_round_mean_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
+                                                    decltype(ntc)::value>),
+                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt,
+                         theta, agents, first, m, c_off, ncols, rho, -lr, momentum, local_steps, theta_out, scale, do_div,
+                         partial, part_off, nb);
+    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt});
+  };
+  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
+  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
+  if (resid_total) hipLaunchKernelGGL(resid_reduce_kernel, dim3(2), dim3(kThreads), 0, s, partial, nb, resid_total);
+  return check_launch(nm);
+}
+
+int dol_ordered_sum_f32(const float* W, int64_t ldw, const int32_t* order, int32_t m, int64_t P,
+                        const float* acc_in, float* acc_out, float scale, hipStream_t s) {
+  DOL_DIMS_OK("dol_ordered_sum_f32", ldw, P);
+  DOL_CHECKED(check_size("dol_ordered_sum_f32", m < 0 || P < 0, P == 0));
+  if (m == 0 && !acc_in) return fail(DOL_EINVAL, "dol_ordered_sum_f32: m == 0 needs acc_in");
+  if (!acc_out || (m > 0 && (!W || !order))) return fail(DOL_EINVAL, "dol_ordered_sum_f32: null pointer");
+  if (m > 0 && ldw < P) return fail(DOL_EINVAL, "dol_ordered_sum_f32: ld < P");
+  if (!(scale > 0.0f)) return fail(DOL_EINVAL, "dol_ordered_sum_f32: scale must be > 0");
+  const bool vec_ok = row_vec_ok(W, ldw) && row_vec_ok(acc_in, 0) && row_vec_ok(acc_out, 0);
+  const ColSplit cs = split_cols(P, vec_ok);
+  const int do_div = scale != 1.0f;
+  if (cs.n4 > 0)
+    hipLaunchKernelGGL(ordered_sum_kernel<f4>, dim3(static_cast<unsigned>(cdiv(cs.n4, kThreads))), dim3(kThreads), 0,
+                       s, W, ldw, order, m, int64_t(0), cs.n4, acc_in, acc_out, scale, do_div);
+  if (cs.tail > 0)
+    hipLaunchKernelGGL(ordered_sum_kernel<float>, dim3(static_cast<unsigned>(cdiv(cs.tail, kThreads))), dim3(kThreads), 0,
+                       s, W, ldw, order, m, cs.n4 * 4, cs.tail, acc_in, acc_out, scale, do_div);
+  return check_launch("dol_ordered_sum_f32");
+}
+
+int dol_ordered_mean_f32(const float* W, int64_t ldw, const int32_t* order, int32_t m, int64_t P,
+                         float* theta, hipStream_t s) {
+  DOL_DIMS_OK("dol_ordered_mean_f32", ldw, P);
+  if (m <= 0) return fail(DOL_EINVAL, "dol_ordered_mean_f32: m must be >= 1 (reference indexes w[0])");
+  if (theta == W) return fail(DOL_EINVAL, "dol_ordered_mean_f32: theta aliases W");
+  return dol_ordered_sum_f32(W, ldw, order, m, P, nullptr, theta, static_cast<float>(m), s);
+}
+
+}  // extern "C"

@@ -71,18 +71,13 @@
 //    (1.35 ms); index by scalar loads (2.1 ms); chunk headers by s_load
 //    instead of vector loads issued with the chunk's DMA (1.135-1.147 vs
 //    1.105-1.12 ms).
-#include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
-#include <stdint.h>
 
-#include "../../include/dol_hip.h"
-#include "dol_common.h"
+#include "dol_launch.h"
 #include "csr_slab_stream.inc"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kCols = 256;                 // slab width (floats): one f4 per lane
 constexpr int kChunk = DOL_SLAB_CHUNK;     // agents per LDS chunk
@@ -135,7 +130,7 @@ __device__ __forceinline__ void dma16(const void* gptr, void* ldst) {
 
 // separately rounded mul, then add (v_pk_mul_f32 / v_pk_add_f32 pairs: 1.18 ms
 // vs 1.33 with the per-component scalar form at 1024 x 101,770, same bits)
-__device__ __forceinline__ f4 fmac(f4 acc, float w, f4 x) { return acc + x * w; }
+__device__ __forceinline__ f4 fmac_pk(f4 acc, float w, f4 x) { return acc + x * w; }
 
 // LDS byte address of entry word `o`'s piece for this lane (stage base + lane * 16 in `lb`)
 __device__ __forceinline__ uint32_t piece_addr(uint32_t o, uint32_t lb) { return o + lb; }
@@ -311,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
           f4 a = vget(r);
           for (int e = bnd[r]; e < bnd[r + 1]; ++e) {
             const int64_t q = int64_t(e >> 1) * 4 + 2 * (e & 1);  // (weight, offset)
-            a = fmac(a, __int_as_float(ent[q]), gather(ent[q + 1]));
+            a = fmac_pk(a, __int_as_float(ent[q]), gather(ent[q + 1]));
           }
           vset(r, a);
         }
@@ -363,8 +358,8 @@ __global__ __launch_bounds__(kThreads) void csr_slab_kernel(
         INN = pair_at(pb + 16 * (K + 2));                                        \
         GNA = gather(IN.o0);                                                     \
         GNB = gather(IN.o1);                                                     \
-        a = fmac(a, __int_as_float(IC.w0), GCA);                                 \
-        a = fmac(a, __int_as_float(IC.w1), GCB);
+        a = fmac_pk(a, __int_as_float(IC.w0), GCA);                              \
+        a = fmac_pk(a, __int_as_float(IC.w1), GCB);
         for (;;) {
           DOL_SLAB_STEP(0, I0, I1, I2, G0a, G0b, G1a, G1b)
           DOL_SLAB_STEP(1, I1, I2, I0, G1a, G1b, G0a, G0b)
@@ -825,8 +820,6 @@ __global__ void slab_tail_kernel(const int32_t* __restrict__ hdr, int64_t blocks
 }
 static_assert(kTailPad <= kEntPad, "the tail pads fit the entry slack");
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // kernel of dol_mix_csr_slab_f32 (dol_slab_set_variant): 0 = the default (3),
 // 2 = pipelined stream (r06), 3 = the stream hand-scheduled (asm; rows of
 // 2^30 floats and more run variant 2); 1 was the retired row loop.  Atomic:
@@ -882,13 +875,7 @@ extern "C" int dol_mix_csr_slab_f32(const float* X, int64_t ldx, int32_t x_rows,
   if (n_items >= (int64_t(1) << 32)) return fail(DOL_EINVAL, "dol_mix_csr_slab_f32: too many workgroups");
   // persistent grid (one workgroup per CU, a multiple of 8) unless there is a
   // single chunk (x_rows <= 64: the stream across items needs nk >= 2)
-  static const int n_cu = [] {
-    int dev = 0, cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cu = 0;
-    return cu;
-  }();
-  const int64_t g_cap = int64_t(n_cu) / 8 * 8;
+  const int64_t g_cap = int64_t(n_cus()) / 8 * 8;
   const int64_t grid = (nk >= 2 && g_cap >= 8) ? std::min<int64_t>(n_items, g_cap) : n_items;
   auto launch = [&](auto kern) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds);

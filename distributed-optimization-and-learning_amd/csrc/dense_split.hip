@@ -62,19 +62,13 @@
 //  * DOL_SPLIT3_XPASS1, the r01 X split pass, one thread per (column, k-group):
 //    224 vs 196 us at 1024 x 101,770 (profiles/r02_split3_xpass.txt).
 //  * DOL_SPLIT3_GROUP_M, the row tiles per XCD group (kGroupM = 8 stayed).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/dol_hip.h"
-#include "dol_common.h"
+#include "dol_launch.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 constexpr int kTile = 256;                            // BM = BN
 constexpr int kRec = 48;                              // bytes per (row, k-group): 3 pieces x 8 bf16
@@ -84,9 +78,6 @@ constexpr int kStages = 3;
 constexpr int kLds = kStages * kStageBytes;           // 144 KiB
 constexpr int kGroupM = 8;                            // row tiles per XCD group
 constexpr int kDmaPerWave = kStageBytes / 1024 / 4;   // 12 LDS-DMA instructions per wave per stage
-
-#define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 __device__ __forceinline__ bool finite_bits(uint32_t u) { return (u & 0x7f800000u) != 0x7f800000u; }
 
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(256) void split3_cols4_kernel(const float* __restri
       const int k = 8 * kg + j;
       const float* row = X + int64_t(k < K ? k : 0) * ldx + p0;
       if (whole) {
-        const f4v q = k < K ? *reinterpret_cast<const f4v*>(row) : f4v{0.f, 0.f, 0.f, 0.f};
+        const f4 q = k < K ? *reinterpret_cast<const f4*>(row) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < 4; ++c) v[c][j] = q[c];
       } else {
@@ -570,8 +561,6 @@ void dense_split3_fx8_kernel(const uint8_t* __restrict__ WA, float* __restrict__
     }
 }
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 struct Split3Geom {
   int64_t Mp, Pp, Kg, bytesA, bytesB;
 };
@@ -820,15 +809,7 @@ extern "C" int dol_mix_dense_split3_f32(const float* W, int64_t ldw, const float
   // halves) in a second launch: 1024 agents x 101,770 = 1592 tiles = 6 x 256 +
   // 56 -> quarters, 2048 agents = 12 x 256 + 112 -> halves.  DOL_SPLIT3_CUS overrides the
   // CU count (tests force the tail path at small sizes; 0 disables it).
-  static const int n_cu = [] {
-    int dev = 0, cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cu = 0;
-    return cu;
-  }();
-  const char* cus_env = getenv("DOL_SPLIT3_CUS");
-  const int64_t cus = cus_env && *cus_env ? atoi(cus_env) : n_cu;
+  const int64_t cus = env_int("DOL_SPLIT3_CUS", n_cus());
   const int64_t tail = cus > 0 ? n_tiles % cus : 0;
   // the fused path's tail is quarters only (256 x 64, one CU each); the split pass also takes halves
   const bool narrow_tail = n_tiles > cus && tail > 0 && (fx ? 4 : 2) * tail <= cus;

@@ -1,0 +1,300 @@
+// dol_launch.h — the host and device pieces that more than one translation
+// unit of libdol_hip.so uses, each written once: launch arithmetic, the
+// runtime-to-template dispatcher, the entry-point preamble, the f4 vector
+// helpers and the mixing epilogues (the config-3 local step among them).
+// Everything here has internal linkage (anonymous namespace), so the kernels
+// instantiated over these types keep one definition per object.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <type_traits>
+
+#include "../../include/dol_hip.h"
+#include "dol_common.h"
+
+// LDS-DMA operands (global_load_lds): the global source and the LDS destination
+#define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
+#define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
+
+namespace {
+using dol::check_launch;
+using dol::fail;
+using dol::g_err;
+
+// ----------------------------------------------------------------------------
+// host-side launch helpers
+// ----------------------------------------------------------------------------
+constexpr int64_t kMaxBlocks = int64_t(1) << 24;
+
+inline int64_t cdiv(int64_t a, int64_t b) { return a / b + (a % b != 0); }
+// a * b saturated at INT64_MAX: block-count checks of absurd sizes must fail, not overflow
+inline int64_t mul_sat(int64_t a, int64_t b) {
+  int64_t r;
+  return __builtin_mul_overflow(a, b, &r) ? INT64_MAX : r;
+}
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool row_vec_ok(const void* base, int64_t ld) { return base == nullptr || (aligned16(base) && (ld % 4) == 0); }
+
+// Split [0, P) into a f4 part and a scalar tail; vec_ok: whether the f4 path
+// is legal for every (base, ld) pair of the call.
+struct ColSplit {
+  bool vec;
+  int64_t n4;    // f4 columns
+  int64_t tail;  // scalar columns after 4*n4 (or all P when !vec)
+};
+inline ColSplit split_cols(int64_t P, bool vec_ok) {
+  if (!vec_ok) return {false, 0, P};
+  return {true, P / 4, P % 4};
+}
+
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v && *v ? atoi(v) : dflt;
+}
+
+// compute units of the current device, asked once; 0 when there is none (each caller has its own fallback)
+inline int n_cus() {
+  static const int n = [] {
+    int dev = 0, cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      cu = 0;
+    return cu > 0 ? cu : 0;
+  }();
+  return n;
+}
+
+// SGD momentum mode of a step: 0 = none, 1 = first step (buf = g), 2 = buf = buf*mom + g
+inline int momentum_mode(float momentum, int first_step) { return (momentum == 0.0f) ? 0 : (first_step ? 1 : 2); }
+
+// Runtime values to template arguments: dispatch(f, Bool{b}, Ints<0, 1, 2>{m})
+// calls the generic lambda f(std::bool_constant<b>{}, std::integral_constant<int, m>{}),
+// one selector per argument, in order.  An int outside its list takes the last value.
+struct Bool { bool v; };
+template <int... Vs> struct Ints { int v; };
+
+template <class F> auto dispatch(F&& f) { return f(); }
+template <class F, class... R> auto dispatch(F&& f, Bool b, R... r);
+template <class F, int V, int... Vs, class... R> auto dispatch(F&& f, Ints<V, Vs...> i, R... r);
+template <class F, class K, class... R> auto dispatch_rest(F& f, K k, R... r) {
+  return dispatch([&](auto... c) { return f(k, c...); }, r...);
+}
+template <class F, class... R> auto dispatch(F&& f, Bool b, R... r) {
+  return b.v ? dispatch_rest(f, std::true_type{}, r...) : dispatch_rest(f, std::false_type{}, r...);
+}
+template <class F, int V, int... Vs, class... R> auto dispatch(F&& f, Ints<V, Vs...> i, R... r) {
+  if constexpr (sizeof...(Vs) == 0) return dispatch_rest(f, std::integral_constant<int, V>{}, r...);
+  else return i.v == V ? dispatch_rest(f, std::integral_constant<int, V>{}, r...) : dispatch(f, Ints<Vs...>{i.v}, r...);
+}
+
+// The opening checks of an entry point, in the order they all use: negative
+// size, nothing to do, null pointer, short leading dimension, aliased output.
+// Returns DOL_OK to go on, kEmpty for an empty problem (the caller returns
+// DOL_OK; the message is cleared), else the refusal.  The two texts that
+// differ between entry points are parameters.
+constexpr int kEmpty = 1;
+inline int check_size(const char* nm, bool negative, bool empty) {
+  if (negative) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (empty) { g_err[0] = '\0'; return kEmpty; }
+  return DOL_OK;
+}
+inline int check_rows(const char* nm, bool negative, bool empty, bool null, bool ld_short, bool alias,
+                      const char* alias_msg = "X and Y alias", const char* ld_msg = "ld < P") {
+  if (const int rc = check_size(nm, negative, empty)) return rc;
+  if (null) return fail(DOL_EINVAL, "%s: null pointer", nm);
+  if (ld_short) return fail(DOL_EINVAL, "%s: %s", nm, ld_msg);
+  if (alias) return fail(DOL_EINVAL, "%s: %s", nm, alias_msg);
+  return DOL_OK;
+}
+#define DOL_CHECKED(call)                                                  \
+  do {                                                                     \
+    if (const int dol_rc_ = (call)) return dol_rc_ == kEmpty ? DOL_OK : dol_rc_; \
+  } while (0)
+constexpr const char* kJacobiAlias = "X and Y alias (Jacobi mix needs two buffers)";
+
+// ----------------------------------------------------------------------------
+// vector helpers: the same kernel body runs on float (tail / unaligned) and
+// f4 (main stream).  All arithmetic is explicit per lane so that each
+// product and sum rounds once, exactly as the reference's torch CPU ops.
+// ----------------------------------------------------------------------------
+typedef float f4 __attribute__((ext_vector_type(4)));  // native 16-B vector (nontemporal builtins need it)
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+using rsrc_t = __amdgpu_buffer_rsrc_t;
+constexpr uint32_t kOOB = 0x80000000u;  // a buffer offset past every range: the access is dropped
+
+template <typename V> struct Vec;
+template <> struct Vec<float> {
+  static constexpr int W = 1;
+};
+template <> struct Vec<f4> {
+  static constexpr int W = 4;
+};
+
+__device__ __forceinline__ float axpy0(float wp, float a, float wn, float b) {
+  // ((+0 + wp*a) + wn*b) with every operation rounded (no contraction)
+  float acc = 0.0f;
+  acc = acc + wp * a;
+  acc = acc + wn * b;
+  return acc;
+}
+__device__ __forceinline__ f4 axpy0(float wp, f4 a, float wn, f4 b) {
+  return f4{axpy0(wp, a.x, wn, b.x), axpy0(wp, a.y, wn, b.y),
+            axpy0(wp, a.z, wn, b.z), axpy0(wp, a.w, wn, b.w)};
+}
+// (ring_steps_kernel with 8-B lanes and R = 22-54: 11.25-11.65 ms vs 11.24-11.27
+// for f4 / R = 22 at eps = 5, 8192 x 2^20, same box: kept f4)
+__device__ __forceinline__ float fmac(float acc, float a, float x) { return acc + a * x; }
+__device__ __forceinline__ f4 fmac(f4 acc, float a, f4 x) {
+  return f4{acc.x + a * x.x, acc.y + a * x.y, acc.z + a * x.z, acc.w + a * x.w};
+}
+__device__ __forceinline__ float vzero(float) { return 0.0f; }
+__device__ __forceinline__ f4 vzero(f4) { return f4{0.f, 0.f, 0.f, 0.f}; }
+__device__ __forceinline__ float vadd(float a, float b) { return a + b; }
+__device__ __forceinline__ f4 vadd(f4 a, f4 b) {
+  return f4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w};
+}
+__device__ __forceinline__ float vdiv(float a, float s) { return a / s; }
+__device__ __forceinline__ f4 vdiv(f4 a, float s) {
+  return f4{a.x / s, a.y / s, a.z / s, a.w / s};
+}
+
+template <typename V, bool NT>
+__device__ __forceinline__ V ldv(const V* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <typename V, bool NT>
+__device__ __forceinline__ void stv(V* p, V v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
+// ----------------------------------------------------------------------------
+// Mixing epilogues.  NoEpi: Y = W X (the gossip round).  DgdEpi: then `steps`
+// local momentum-SGD iterations per agent on a separable synthetic loss —
+// BASELINE config 3, decentralised gradient descent in the reference's round
+// order (DIST/simulators.py:147-162: consensus, then local_update with the
+// optimizer of DIST/clients.py:43-49) — so a round streams X, the targets and
+// the momentum once.  Rounding as oracle_dgd_local_f32:
+//   OBJ 0 least squares  g = x - t;   OBJ 1 logistic  g = -t / (1 + exp(t x))
+//   MODE 0 plain SGD; 1 momentum, first step (buf = g); 2 momentum (buf = buf*mom + g)
+//   x = fma(-lr, d, x)
+// load() is issued with the mixing loads; apply() runs after the mix.
+// ----------------------------------------------------------------------------
+// The local steps on one coordinate: the one place this arithmetic is written
+// (DgdEpi on the agent-major bank, csr_pm_kernel on the parameter-major one).
+// e: the epilogue's arguments, read where they are used (e.steps, e.mom, e.neg_lr).
+template <int OBJ, int MODE, class E>
+__device__ __forceinline__ float dgd_local_steps(float x, float t, float& b, const E& e) {
+  for (int s = 0; s < e.steps; ++s) {
+    float g;
+    if constexpr (OBJ == 0) g = x - t;
+    else g = -t / (1.0f + expf(t * x));
+    float d = g;
+    if constexpr (MODE != 0) {
+      if (MODE == 1 && s == 0) b = g;
+      else b = b * e.mom + g;
+      d = b;
+    }
+    x = __builtin_fmaf(e.neg_lr, d, x);
+  }
+  return x;
+}
+
+struct Empty {};
+struct NoEpi {
+  template <typename V> __device__ __forceinline__ Empty load(int, int64_t) const { return {}; }
+  template <typename V> __device__ __forceinline__ V apply(V y, Empty, int, int64_t) const { return y; }
+};
+
+template <typename V> struct DgdState { V t, b; };
+
+template <int OBJ, int MODE>
+struct DgdEpi {
+  const float* __restrict__ T; int64_t ldt;
+  float* __restrict__ M; int64_t ldm;
+  float neg_lr, mom;
+  int steps;
+  // Target / momentum rows are read once: buffer loads with the nontemporal
+  // policy (aux 3 = sc0 nt), so they do not push the X halo rows -- re-read by
+  // the next row group's tile, 1024 workgroups later -- out of the XCD's L2.
+  // With plain loads the ring round read 1.16x its bytes (14.97 vs 12.88 GB
+  // at 1024 x 2^20, least squares + momentum) and ran 3.58-3.59 ms; with these
+  // 12.90 GB = 1.00x and 3.44-3.45 ms (profiles/r06f_dgd_epi_policy.jsonl; sc0
+  // sc1 without nt: no change).  DOL_DGD_EPI_NT=0 restores plain loads, 1 the
+  // compiler's nontemporal global loads (the switch stays: it is this runtime
+  // branch, inside every DGD kernel).
+  int nt;
+
+  template <typename V> __device__ __forceinline__ V ld(const float* row, int64_t cf) const {
+    const V* p = reinterpret_cast<const V*>(row + cf);
+    if constexpr (sizeof(V) == 16) {
+      if (nt == 3) {
+        const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, 0x7ffffff0, 0x00020000);
+        return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, uint32_t(cf) * 4u, 0, 3));
+      }
+      if (nt == 1) return __builtin_nontemporal_load(p);
+    }
+    return *p;
+  }
+  template <typename V> __device__ __forceinline__ DgdState<V> load(int r, int64_t cf) const {
+    DgdState<V> st;
+    st.t = ld<V>(T + int64_t(r) * ldt, cf);
+    if constexpr (MODE == 2) st.b = ld<V>(M + int64_t(r) * ldm, cf);
+    else st.b = vzero(V{});
+    return st;
+  }
+  template <typename V> __device__ __forceinline__ V apply(V y, DgdState<V> st, int r, int64_t cf) const {
+    if constexpr (Vec<V>::W == 1) {
+      y = dgd_local_steps<OBJ, MODE>(y, st.t, st.b, *this);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float bj = st.b[j];
+        y[j] = dgd_local_steps<OBJ, MODE>(y[j], st.t[j], bj, *this);
+        st.b[j] = bj;
+      }
+    }
+    if constexpr (MODE != 0) __builtin_nontemporal_store(st.b, reinterpret_cast<V*>(M + int64_t(r) * ldm + cf));
+    return y;
+  }
+};
+
+// validation + dispatch of the BASELINE config-3 round (mix + local steps)
+struct DgdArgs {
+  const float* T; int64_t ldt; float* M; int64_t ldm;
+  int32_t objective, steps; float lr, momentum; int first_step;
+};
+
+inline int check_dgd(const char* nm, const DgdArgs& d, int64_t P, bool* evec, int* mode) {
+  if (!d.T) return fail(DOL_EINVAL, "%s: null target", nm);
+  if (d.objective != 0 && d.objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 (least squares) or 1 (logistic)", nm);
+  if (d.steps < 1) return fail(DOL_EINVAL, "%s: local_steps must be >= 1", nm);
+  if (d.ldt < P) return fail(DOL_EINVAL, "%s: ldt < P", nm);
+  *mode = momentum_mode(d.momentum, d.first_step);
+  if (*mode != 0 && (!d.M || d.ldm < P)) return fail(DOL_EINVAL, "%s: momentum needs a momentum buffer with ldm >= P", nm);
+  *evec = row_vec_ok(d.T, d.ldt) && (*mode == 0 || row_vec_ok(d.M, d.ldm));
+  return DOL_OK;
+}
+
+// Checks d (unless the problem is empty: the mix's own preamble then answers)
+// and calls f(epi, epi_vec_ok) with the epilogue of d's objective and mode.
+template <class F>
+int with_dgd_epi(const char* nm, const DgdArgs& d, bool empty, int64_t P, F&& f) {
+  bool evec = false;
+  int mode = 0;
+  if (!empty) {
+    const int rc = check_dgd(nm, d, P, &evec, &mode);
+    if (rc) return rc;
+  }
+  static const int nt_env = env_int("DOL_DGD_EPI_NT", 3);
+  // buffer offsets are 32-bit (rows of < 2^29 floats); longer rows: plain loads
+  const int nt = (nt_env == 3 && P > (int64_t(1) << 29) - 16) ? 0 : nt_env;
+  return dispatch([&](auto obj, auto md) {
+    return f(DgdEpi<decltype(obj)::value, decltype(md)::value>{d.T, d.ldt, d.M, d.ldm, -d.lr, d.momentum, d.steps, nt}, evec);
+  }, Ints<0, 1>{d.objective}, Ints<0, 1, 2>{mode});
+}
+
+}  // namespace

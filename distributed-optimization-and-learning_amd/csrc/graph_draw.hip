@@ -15,11 +15,7 @@
 // Bytes: n^2 * 4 written once (HBM-bound store stream), nothing read.
 // The draw is a synthetic workload (not a reference topology): seeded and
 // deterministic, but not the torch generator's stream.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/dol_hip.h"
-#include "dol_common.h"
+#include "dol_launch.h"
 
 namespace {
 

@@ -64,19 +64,13 @@
 // MFMA = a k-ordered f32 fma chain; the reference's torch CPU GEMMs use a
 // different blocking, so this path is tolerance-checked (tests/test_mlp_gpu.py),
 // not bit-exact.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <math.h>
-#include <type_traits>
+#include <stdio.h>
 
-#include "../../include/dol_hip.h"
-#include "dol_common.h"
+#include "dol_launch.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWaves = 4;
@@ -115,7 +109,7 @@ struct MlpArgs {
 #endif
 
 // Gradient term + optimizer update of N parameters (same rounding sequence as
-// prox_sgd_lane in dol_hip.hip).  All loads of the batch are issued before any
+// prox_sgd_lane in admm.hip).  All loads of the batch are issued before any
 // store (load() first, e.g. ahead of the MFMAs that produce the gradients, then
 // commit()): the rows are plain float*, so a load-update-store per element
 // would serialise one memory round trip per element.  Loads are unconditional
@@ -166,9 +160,6 @@ struct ParamBatch {
     }
   }
 };
-
-#define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 // s_waitcnt vmcnt(n) for a wave-uniform runtime n (the immediate must be a constant)
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -223,10 +214,7 @@ inline int64_t fwd_union_floats(int B, int h, int c) {
 }
 
 // Buffer-descriptor memory ops of mlp_dw1_kernel: dead lanes point out of range
-// (loads return 0, stores are dropped).
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-constexpr uint32_t kOOB = 0x80000000u;  // any lane offset >= every buffer's size
-
+// (loads return 0, stores are dropped; rsrc_t and kOOB are dol_launch.h's).
 __device__ __forceinline__ rsrc_t make_rsrc(const float* p, int64_t nbytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, static_cast<int>(nbytes), 0x00020000);
 }
@@ -695,7 +683,7 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
       ldx_agent % 4)
     return fail(DOL_EINVAL, "dol_mlp_step_f32: w and X rows must be 16-byte aligned");
   if (alpha && !theta) return fail(DOL_EINVAL, "dol_mlp_step_f32: alpha without theta");
-  const int mode = (momentum == 0.0f) ? 0 : (first_step ? 1 : 2);
+  const int mode = momentum_mode(momentum, first_step);
   if (update && mode != 0 && !mom) return fail(DOL_EINVAL, "dol_mlp_step_f32: momentum needs the mom buffer");
   if (!update && !grad) return fail(DOL_EINVAL, "dol_mlp_step_f32: update=0 needs a grad buffer to write");
   MlpArgs a{w, ldw, grad, ldg, mom, ldm, theta, alpha, lda, X, ldx_agent, ldx_row, labels, ldy_agent, loss,
@@ -707,8 +695,7 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
   // (fused step + exact mix, 1024 agents): 1.378 vs 1.400 ms, the local step
   // 0.457-0.462 vs 0.477-0.479 ms, three alternating trials; the step alone
   // 0.475-0.480 vs 0.490-0.494 (profiles/r06m_mlp_order.jsonl).  Same bits.
-  static const int f1_keep = [] { const char* e = getenv("DOL_MLP_F1_KEEP"); return e ? atoi(e) : 1; }();
-  static const int dw1_rev = [] { const char* e = getenv("DOL_MLP_DW1_REVERSE"); return e ? atoi(e) : 1; }();
+  static const int f1_keep = env_int("DOL_MLP_F1_KEEP", 1), dw1_rev = env_int("DOL_MLP_DW1_REVERSE", 1);
   a.f1_keep = f1_keep;
   a.dw1_reverse = dw1_rev;
   // r06: the forward's second workgroup slot of every CU (blocks [n_cu, 2 n_cu))
@@ -720,13 +707,7 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
   // "count,mode" overrides (read per call; "0" = off; mode 2 = the odd blocks of
   // [0, 2 n_cu), measured slower)
   {
-    static const int n_cu = [] {
-      int dev = 0, cu = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        cu = 0;
-      return cu;
-    }();
+    const int n_cu = n_cus();
     const char* e = getenv("DOL_MLP_FWD_STAGGER");  // read per call (A/B in one process)
     int cnt = (n_cu > 0 && n_agents >= 4 * n_cu) ? 6 : 0, mode = 1;
     if (e && sscanf(e, "%d,%d", &cnt, &mode) < 1) cnt = 0;
@@ -746,9 +727,9 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
   const int64_t n_blk2 = int64_t((d + 31) / 32) * ((int64_t(n_agents) + 7) / 8 * 8);
   if (n_blk2 > (int64_t(1) << 31) - 1) return fail(DOL_EINVAL, "dol_mlp_step_f32: too many W1 tiles for one launch");
   const dim3 grid2(static_cast<unsigned>(n_blk2));
-  auto go = [&](auto ks, auto upd_c, auto th, auto al) {
+  auto go = [&](auto ks, auto upd_c, auto terms) {
     constexpr int KS = decltype(ks)::value, U = decltype(upd_c)::value;
-    constexpr bool TH = decltype(th)::value, AL = decltype(al)::value;
+    constexpr bool TH = decltype(terms)::value >= 1, AL = decltype(terms)::value == 2;
     auto fwd = [&](auto kern) {
       if (lds > 65536)  // above the default dynamic-LDS cap (gfx950 has 160 KiB per CU)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -759,27 +740,7 @@ extern "C" int dol_mlp_step_f32(float* w, int64_t ldw, float* grad, int64_t ldg,
     else fwd(mlp_fwd_kernel<4, U, TH, AL>);
     hipLaunchKernelGGL((mlp_dw1_kernel<KS, U, TH, AL>), grid2, block, 0, s, a, ws, n_agents);
   };
-  auto by_upd = [&](auto ks, auto th, auto al) {
-    using std::integral_constant;
-    switch (upd) {
-      case 0: go(ks, integral_constant<int, 0>{}, th, al); break;
-      case 1: go(ks, integral_constant<int, 1>{}, th, al); break;
-      case 2: go(ks, integral_constant<int, 2>{}, th, al); break;
-      default: go(ks, integral_constant<int, 3>{}, th, al); break;
-    }
-  };
-  using K16 = std::integral_constant<int, 16>;
-  using K32 = std::integral_constant<int, 32>;
-  using T = std::true_type;
-  using F = std::false_type;
-  if (B <= 32) {
-    if (!theta) by_upd(K16{}, F{}, F{});
-    else if (!alpha) by_upd(K16{}, T{}, F{});
-    else by_upd(K16{}, T{}, T{});
-  } else {
-    if (!theta) by_upd(K32{}, F{}, F{});
-    else if (!alpha) by_upd(K32{}, T{}, F{});
-    else by_upd(K32{}, T{}, T{});
-  }
+  // the proximal terms: 0 none, 1 theta, 2 theta and alpha (alpha alone was refused above)
+  dispatch(go, Ints<16, 32>{B <= 32 ? 16 : 32}, Ints<0, 1, 2, 3>{upd}, Ints<0, 1, 2>{(theta != nullptr) + (alpha != nullptr)});
   return dol::check_launch("dol_mlp_step_f32");
 }

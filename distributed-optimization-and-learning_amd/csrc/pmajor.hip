@@ -1,7 +1,7 @@
 // pmajor.hip — the sparse gossip mix on the PARAMETER-MAJOR ("transposed")
 // bank layout, and the layout conversion.  Part of libdol_hip.so.
 //
-// Layout.  The agent-major bank (row k = agent k's P parameters, dol_hip.hip)
+// Layout.  The agent-major bank (row k = agent k's P parameters, ring.hip / csr.hip)
 // is what the notebooks' nn.Module views need.  For synthetic many-agent
 // workloads whose local steps are per coordinate (BASELINE config 3: 1024-8192
 // agents x 2^20 on a random-regular W) the engine can hold the bank
@@ -40,31 +40,14 @@
 //  * DOL_PM_VARIANT 1 / 4, the plain mix with default-policy (not
 //    nontemporal) LDS-DMA loads, and a copy y = x in the same geometry (the
 //    structure's own ceiling): measurement only.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <stdlib.h>
-
 #include <algorithm>
 #include <atomic>
 
-#include "../../include/dol_hip.h"
-#include "dol_common.h"
-
-#define DOL_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define DOL_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
+#include "dol_launch.h"
 
 namespace {
-using dol::check_launch;
-using dol::fail;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-
 constexpr int kMaxAgents = 8192;          // one p-row image fits a 32 KiB stage
 constexpr int kT1 = 1024;                 // threads per workgroup (16 waves, one workgroup per CU)
-constexpr uint32_t kOOB = 0x80000000u;    // a buffer offset past every range: the store is dropped
 constexpr int kNT = 2;                    // cache-policy bits of the LDS-DMA loads and the stores: nontemporal
 
 __device__ __forceinline__ void wait_vmcnt(int n) {
@@ -158,32 +141,16 @@ __device__ __forceinline__ f4 mix_quad(const Quad& Q, const float* __restrict__ 
 // dol_dgd_csr_f32, transposed): after the mix, `steps` local momentum-SGD
 // iterations on the separable loss, per coordinate (OBJ 0 least squares
 // g = x - t, 1 logistic g = -t / (1 + exp(t x)); MODE 0 plain SGD, 1 first
-// momentum step, 2 momentum), x = fma(-lr, d, x) — the arithmetic of DgdEpi /
-// oracle_dgd_local_f32.  The target (and momentum) p-rows of a stage come in
-// by the same LDS-DMA as X, behind the X image.
+// momentum step, 2 momentum), x = fma(-lr, d, x) — dgd_local_steps of
+// dol_launch.h, the arithmetic of DgdEpi / oracle_dgd_local_f32.  The target
+// (and momentum) p-rows of a stage come in by the same LDS-DMA as X, behind
+// the X image.
 struct PmDgd {
   const float* T; int64_t ldt;
   float* M; int64_t ldm;
   float neg_lr, mom;
   int steps;
 };
-
-template <int OBJ, int MODE>
-__device__ __forceinline__ float dgd_local(float x, float t, float& b, const PmDgd& e) {
-  for (int s = 0; s < e.steps; ++s) {
-    float g;
-    if constexpr (OBJ == 0) g = x - t;
-    else g = -t / (1.0f + expf(t * x));
-    float d = g;
-    if constexpr (MODE != 0) {
-      if (MODE == 1 && s == 0) b = g;
-      else b = b * e.mom + g;
-      d = b;
-    }
-    x = __builtin_fmaf(e.neg_lr, d, x);
-  }
-  return x;
-}
 
 // Mix one stage image (sr p-rows of xw floats at im0, p-rows p0 ..) and store
 // its rows of YT (and, OBJ >= 0, run the local steps first: target / momentum
@@ -217,8 +184,8 @@ __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __r
         const f4 tv = *reinterpret_cast<const f4*>(tim0 + prc * nw + 4 * qc);
         if constexpr (MODE == 2) bv = *reinterpret_cast<const f4*>(mim0 + prc * nw + 4 * qc);
         float b0 = bv.x, b1 = bv.y, b2 = bv.z, b3 = bv.w;
-        y = f4{dgd_local<OBJ, MODE>(y.x, tv.x, b0, e), dgd_local<OBJ, MODE>(y.y, tv.y, b1, e),
-               dgd_local<OBJ, MODE>(y.z, tv.z, b2, e), dgd_local<OBJ, MODE>(y.w, tv.w, b3, e)};
+        y = f4{dgd_local_steps<OBJ, MODE>(y.x, tv.x, b0, e), dgd_local_steps<OBJ, MODE>(y.y, tv.y, b1, e),
+               dgd_local_steps<OBJ, MODE>(y.z, tv.z, b2, e), dgd_local_steps<OBJ, MODE>(y.w, tv.w, b3, e)};
         bv = f4{b0, b1, b2, b3};
       }
       const uint32_t off = static_cast<uint32_t>((pr * ldy + 4 * q) * 4);
@@ -366,22 +333,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 // and the _ex entry points take the order per call
 std::atomic<int> g_pm_nseg{0};
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
-int n_cus() {
-  static const int n = [] {
-    int dev = 0, cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cu = 0;
-    return cu;
-  }();
-  return n;
-}
-
 }  // namespace
 
 extern "C" {
@@ -475,15 +426,11 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   if (obj < 0) {
     if (big) go(csr_pm_kernel<kT1, 8192, 5, 2>);
     else go(csr_pm_kernel<kT1, 16384, 2, 1>);
-  } else if (mode == 2) {  // small geometry only
-    if (obj == 0) go(csr_pm_kernel<kT1, 20480, 2, 1, 0, 2>);
-    else go(csr_pm_kernel<kT1, 20480, 2, 1, 1, 2>);
-  } else if (obj == 0) {
-    if (mode == 0) go(csr_pm_kernel<kT1, 16384, 2, 1, 0, 0>);
-    else go(csr_pm_kernel<kT1, 16384, 2, 1, 0, 1>);
-  } else {
-    if (mode == 0) go(csr_pm_kernel<kT1, 16384, 2, 1, 1, 0>);
-    else go(csr_pm_kernel<kT1, 16384, 2, 1, 1, 1>);
+  } else {  // small geometry only; mode 2 stages the momentum image too
+    dispatch([&](auto oc, auto mc) {
+      constexpr int O = decltype(oc)::value, M = decltype(mc)::value;
+      go(csr_pm_kernel<kT1, (M == 2 ? 20480 : 16384), 2, 1, O, M>);
+    }, Ints<0, 1>{obj}, Ints<0, 1, 2>{mode});
   }
   return check_launch(nm);
 }
@@ -521,7 +468,7 @@ int dol_dgd_csr_pm_ex_f32(const float* XT, int64_t ldx, int32_t x_rows, float* Y
   const char* nm = "dol_dgd_csr_pm_f32";
   if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
   if (local_steps < 1) return fail(DOL_EINVAL, "%s: local_steps must be >= 1", nm);
-  const int mode = momentum == 0.0f ? 0 : (first_step ? 1 : 2);
+  const int mode = momentum_mode(momentum, first_step);
   const PmDgd e{TT, ldt, mode ? MT : nullptr, mode ? ldm : 0, -lr, momentum, local_steps};
   return mix_csr_pm_impl(nm, XT, ldx, x_rows, YT, ldy, n_rows, P, rowptr, col, val, objective, mode, e, nseg, s);
 }

@@ -43,8 +43,13 @@ def _unbundle(name, tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    return _unbundle("dol_hip.o", tmp_path_factory)
+def ring_code_object(tmp_path_factory):
+    return _unbundle("ring.o", tmp_path_factory)
+
+
+@pytest.fixture(scope="module")
+def admm_code_object(tmp_path_factory):
+    return _unbundle("admm.o", tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
@@ -64,14 +69,14 @@ def _disasm(co, sym):
                           check=True, capture_output=True, text=True).stdout
 
 
-def test_ring_stream_dma_waits_are_counted(code_object):
-    ks = _kernels(code_object, "ring_stream_dma_kernel")
+def test_ring_stream_dma_waits_are_counted(ring_code_object):
+    ks = _kernels(ring_code_object, "ring_stream_dma_kernel")
     assert ks, "no ring_stream_dma_kernel instantiations in the code object"
     for k in ks:
         m = re.search(r"ring_stream_dma_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", k)
         assert m, k
         S, D, PF, sync = map(int, m.groups())
-        asm = _disasm(code_object, k)
+        asm = _disasm(ring_code_object, k)
         waits = [int(v) for v in re.findall(r"s_waitcnt vmcnt\((\d+)\)", asm)]
         assert waits, f"{k}: no vmcnt waits"
         assert set(waits) <= {2 * D - 2, 0}, f"{k}: unexpected waits {sorted(set(waits))} (expected {2 * D - 2} / 0)"
@@ -110,16 +115,16 @@ def test_split3_fxw_waits_are_counted(split_code_object):
     assert not re.search(r"global_load_dword[^x_]|global_load_dwordx[24]\b|buffer_load", asm), "unexpected vector loads"
 
 
-def test_admm_round_mean_is_packed_and_counted(code_object):
+def test_admm_round_mean_is_packed_and_counted(admm_code_object):
     """The one-pass FedADMM round + mean (admm_ls_round_mean_kernel, f4
     columns): packed fp32 steps (v_pk_fma_f32 for the SGD update), row stores
     as buffer stores (dead lanes dropped out of range, so every lane issues
     the same memory ops) and counted vmcnt waits inside the agent loop -- not
     only full drains."""
-    ks = [k for k in _kernels(code_object, "admm_ls_round_mean_kernel") if "Dv4_f" in k]
+    ks = [k for k in _kernels(admm_code_object, "admm_ls_round_mean_kernel") if "Dv4_f" in k]
     assert ks, "no f4 admm_ls_round_mean_kernel instantiations"
     for k in ks:
-        asm = _disasm(code_object, k)
+        asm = _disasm(admm_code_object, k)
         assert "v_pk_fma_f32" in asm, k
         assert asm.count("buffer_store_dwordx4") >= 3, k  # w, alpha, momentum rows
         waits = [int(v) for v in re.findall(r"s_waitcnt vmcnt\((\d+)\)", asm)]

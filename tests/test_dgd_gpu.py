@@ -64,8 +64,11 @@ def test_dgd_ring_vs_oracle(objective, momentum, first, steps, n, P, gpu):
 @pytest.mark.parametrize("objective", ["least_squares", "logistic"])
 @pytest.mark.parametrize("n,P,deg", [(16, 4099, 4), (600, 256, 4), (33, 4096, 6), (520, 4098, 4)])
 def test_dgd_csr_vs_oracle(objective, n, P, deg, gpu):
-    """Covers the XCD-pinned CSR kernel (n >= 512), the 4 KiB-tile one, the
-    leftover f4 columns and the scalar tail, each with the epilogue."""
+    """The CSR round with momentum continuing, at four graph sizes and degrees.
+    (600, 256) runs the XCD-pinned f4 kernel (n >= 512) and (33, 4096) the
+    4 KiB-tile f4 kernel; 4099 and 4098 are leading dimensions that are no
+    multiple of 4, so those two run the scalar kernel on every column
+    (test_dgd_csr_momentum_modes_vs_oracle has them on the f4 kernels)."""
     csr = G.random_regular_csr(n, deg, seed=3)
     X, T, M = _inputs(n, P, n * P)
     Xd, Td, Md = dev(X, gpu), dev(T, gpu), dev(M, gpu)
@@ -76,6 +79,77 @@ def test_dgd_csr_vs_oracle(objective, n, P, deg, gpu):
     Y, Mw = oracle.dgd_local(oracle.mix_csr(X, csr.rowptr, csr.col, csr.val), T, M, objective, 2, 0.1, 0.5, False)
     _check(Yd.cpu().numpy(), Y, objective)
     _check(Md.cpu().numpy(), Mw, objective)
+
+
+MODES = [(0.0, False), (0.5, True), (0.5, False)]  # DgdEpi<., 0>, <., 1>, <., 2>
+
+
+def _rows(a, ld, gpu, fill=float("nan")):
+    """Device copy of a [n, P] array in rows of leading dimension ld (the padding holds `fill`)."""
+    t = torch.full((a.shape[0], ld), fill, device=gpu)
+    t[:, :a.shape[1]] = torch.from_numpy(a).to(gpu)
+    return t
+
+
+@pytest.mark.parametrize("objective", ["least_squares", "logistic"])
+@pytest.mark.parametrize("momentum,first", MODES)
+@pytest.mark.parametrize("n,P,deg", [(16, 4099, 4), (520, 4098, 4), (520, 4102, 4)])
+def test_dgd_csr_momentum_modes_vs_oracle(objective, momentum, first, n, P, deg, gpu):
+    """Every momentum mode of the CSR round's epilogue on the f4 kernels.  The
+    rows have a leading dimension that is a multiple of 4 (P rounded up), so
+    the f4 path is legal (with ld = P odd or = 2 mod 4 everything would run on
+    the scalar kernel):
+      (16, 4099):  csr_mix_kernel<f4> on 1024 f4 columns (the 4 KiB tile) + a 3-column scalar tail;
+      (520, 4098): csr_xcd_kernel (>= 512 rows) on all 1024 = 32 x 32 f4 columns + a 2-column tail;
+      (520, 4102): csr_xcd_kernel on 1024 f4 columns, csr_mix_kernel<f4> on the one f4 column left
+                   over, + a 2-column tail.
+    The padding columns of Y and the momentum stay as they were."""
+    ld = (P + 3) // 4 * 4
+    csr = G.random_regular_csr(n, deg, seed=3)
+    X, T, M = _inputs(n, P, n * P + 1)
+    Xd, Td, Md, Yd = _rows(X, ld, gpu), _rows(T, ld, gpu), _rows(M, ld, gpu), _rows(np.zeros_like(X), ld, gpu, 5.0)
+    G.MixingPlan(csr, gpu).apply_dgd(Xd, Yd, Td, mom=Md if momentum else None, objective=objective, steps=2, lr=0.1,
+                                     momentum=momentum, first_step=first, P=P)
+    torch.cuda.synchronize()
+    Y, Mw = oracle.dgd_local(oracle.mix_csr(X, csr.rowptr, csr.col, csr.val), T, M if momentum else None, objective,
+                             2, 0.1, momentum, first)
+    _check(Yd[:, :P].cpu().numpy(), Y, objective)
+    if momentum:
+        _check(Md[:, :P].cpu().numpy(), Mw, objective)
+    assert (Yd[:, P:] == 5.0).all() and torch.isnan(Md[:, P:]).all(), "padding columns written"
+
+
+@pytest.mark.parametrize("objective", ["least_squares", "logistic"])
+@pytest.mark.parametrize("momentum,first", MODES)
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("n", [1, 2, 5])
+def test_dgd_ring_edges_modes_vs_oracle(objective, momentum, first, n, extra, gpu):
+    """dol_dgd_ring_edges_f32 across objective x momentum mode: rows 0 and
+    n - 1 against the local steps on the oracle's ring mix with halos, the
+    interior rows and their momentum untouched.  P = 4099 in rows of
+    ld = 4099 + extra: extra = 0 (odd ld) takes the all-scalar kernel,
+    extra = 1 (ld = 4100) the f4 kernel on 1024 columns + a 3-column tail.
+    n = 1 is the one-row launch that uses both halos."""
+    P, ld = 4099, 4099 + extra
+    rng = np.random.default_rng(n * 7 + extra)
+    X, T, M = _inputs(n, P, n + extra)
+    hp, hn = (rng.standard_normal(P).astype(np.float32) for _ in range(2))
+    wp, wn = rng.random(n).astype(np.float32), rng.random(n).astype(np.float32)
+
+    def rows(a):
+        return _rows(a, ld, gpu)
+    Xd, Yd, Td, Md = rows(X), rows(np.full((n, P), 5.0, np.float32)), rows(T), rows(M)
+    ops.dgd_ring_edges(Xd, Yd, dev(wp, gpu), dev(wn, gpu), Td, dev(hp, gpu), dev(hn, gpu), mom=Md if momentum else None,
+                       objective=objective, steps=2, lr=0.05, momentum=momentum, first_step=first, P=P, n_rows=n)
+    torch.cuda.synchronize()
+    Y, Mw = oracle.dgd_local(oracle.mix_ring(X, wp, wn, hp, hn), T, M if momentum else None, objective, 2, 0.05,
+                             momentum, first)
+    got, gm, edges = Yd[:, :P].cpu().numpy(), Md[:, :P].cpu().numpy(), [0, n - 1]
+    _check(got[edges], Y[edges], objective)
+    assert (got[1:n - 1] == 5.0).all(), "interior rows touched"
+    if momentum:
+        _check(gm[edges], Mw[edges], objective)
+    assert bits_equal(gm[1:n - 1], M[1:n - 1]), "interior momentum touched"
 
 
 def test_dgd_ring_halos_match_wraparound(gpu):

@@ -7,7 +7,7 @@ caching allocator an overrun lands in slack; with a dol_bank_alloc block
 mapped to exactly rows * ld * 4 bytes (rounded to the 2 MiB granularity) it
 faults, so every kernel must stay inside its rows.
 
-Restated (csrc/dol_hip.hip, function and index expressions named per case):
+Restated (csrc/ring.hip and csrc/csr.hip, function and index expressions named per case):
   * ring_mix_dma_kernel<4, DgdEpi, true, false> -- the ring DGD round's float4 body
     (mix_ring_impl: grid nct * cdiv(n, 4)); R + 2 row loads per block at
     min(r0 - 1 + k, r1) through row() (halo pointers below 0 / from n), the

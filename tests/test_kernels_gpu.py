@@ -325,7 +325,7 @@ def _gamma_bound(W, X):
     return (K * u / (1 - K * u)) * (np.abs(W.astype(np.float64)) @ np.abs(X.astype(np.float64)))
 
 
-@pytest.mark.parametrize("M,K,P", [(256, 256, 1024), (130, 37, 1031), (64, 64, 3)])
+@pytest.mark.parametrize("M,K,P", [(256, 256, 1024), (130, 37, 1031), (64, 64, 3), (66, 37, 1032)])
 def test_mix_dense_identity_and_permutation_exact(M, K, P, gpu):
     rng = np.random.default_rng(M + K)
     X = rng.standard_normal((K, P)).astype(np.float32)
@@ -824,6 +824,66 @@ def test_admm_step_dual_equals_two_calls(mom, first, extra, gpu):
     assert bits_equal(ad[:, :P].cpu().numpy(), a1)
     assert bits_equal(gd[:, :P].cpu().numpy(), g1)
     if mom != 0:
+        assert bits_equal(bd[:, :P].cpu().numpy(), b1)
+
+
+@pytest.mark.parametrize("variant", ["avg", "prox", "admm", "admm_dual"])
+@pytest.mark.parametrize("mom,first", [(0.0, False), (0.5, True), (0.5, False)])
+@pytest.mark.parametrize("extra", [0, 1])
+def test_prox_step_without_grad_write_vs_oracle(variant, mom, first, extra, gpu):
+    """write_grad=False in every momentum mode of dol_prox_admm_sgd_f32 (no
+    theta, theta, theta and alpha) and of dol_admm_step_dual_f32: the same w,
+    momentum (and alpha) as with the write, and g left as it was.  P = 1031 in
+    rows of ld = 1031 + extra: extra = 0 (odd ld) is the all-scalar path,
+    extra = 1 (ld = 1032) 257 f4 columns + a 3-column tail."""
+    rng = np.random.default_rng(37)
+    n, P = 4, 1031
+    w, g, b = (rng.standard_normal((n, P)).astype(np.float32) for _ in range(3))
+    th = rng.standard_normal(P).astype(np.float32) if variant != "avg" else None
+    al = rng.standard_normal((n, P)).astype(np.float32) if variant.startswith("admm") else None
+    wd, gd, bd = (padded(a, gpu, extra) for a in (w, g, b))
+    ad = padded(al, gpu, extra) if al is not None else None
+    kw = dict(buf=bd, rho=0.1, lr=0.05, momentum=mom, first_step=first, write_grad=False, P=P)
+    if variant == "admm_dual":
+        ops.admm_step_dual(wd, gd, dev(th, gpu), ad, **kw)
+    else:
+        ops.prox_admm_sgd(wd, gd, theta=None if th is None else dev(th, gpu), alpha=ad, **kw)
+    torch.cuda.synchronize()
+    w1, b1, _ = oracle.prox_admm_sgd(w, b, g, th, al, 0.1, 0.05, mom, first)
+    assert bits_equal(wd[:, :P].cpu().numpy(), w1)
+    if al is not None:
+        a1 = oracle.admm_dual(al, w1, th, 0.1)[0] if variant == "admm_dual" else al
+        assert bits_equal(ad[:, :P].cpu().numpy(), a1)
+    assert bits_equal(gd[:, :P].cpu().numpy(), g), "g written"
+    if mom != 0:
+        assert bits_equal(bd[:, :P].cpu().numpy(), b1)
+
+
+@pytest.mark.parametrize("mom", [0.0, 0.5])
+@pytest.mark.parametrize("extra", [0, 1])
+def test_dual_and_client_round_without_residuals(mom, extra, gpu):
+    """dol_admm_dual_f32 and dol_admm_ls_round_f32 with no residual outputs
+    (the kernels without the block reductions).  P = 1031 in rows of
+    ld = 1031 + extra: extra = 0 is the all-scalar path, extra = 1 f4 + tail."""
+    rng = np.random.default_rng(41)
+    n, P = 5, 1031
+    w, al, t, b = (rng.standard_normal((n, P)).astype(np.float32) for _ in range(4))
+    th = rng.standard_normal(P).astype(np.float32)
+    ad = padded(al, gpu, extra)
+    ops.admm_dual(ad, padded(w, gpu, extra), dev(th, gpu), 0.1, P=P)
+    torch.cuda.synchronize()
+    assert bits_equal(ad[:, :P].cpu().numpy(), oracle.admm_dual(al, w, th, 0.1)[0])
+    order, first = np.array([3, 0, 4], np.int32), np.array([1, 0, 0], np.int32)
+    wd, ad, td, bd = (padded(a, gpu, extra) for a in (np.zeros_like(w), al, t, b))
+    ops.admm_ls_round(wd, ad, td, dev(th, gpu), agents=dev(order, gpu, torch.int32), first=dev(first, gpu, torch.int32),
+                      buf=bd if mom else None,
+                      rho=0.1, lr=0.05, momentum=mom, local_steps=2, P=P)
+    torch.cuda.synchronize()
+    w1, b1, a1, _, _ = oracle.admm_ls_round(np.zeros_like(w), b if mom else None, al, t, th, order, first, 0.1, 0.05,
+                                            mom, 2)
+    assert bits_equal(wd[:, :P].cpu().numpy()[order], w1[order])
+    assert bits_equal(ad[:, :P].cpu().numpy(), a1)
+    if mom:
         assert bits_equal(bd[:, :P].cpu().numpy(), b1)
 
 
