@@ -27,6 +27,29 @@
 // out-of-range lanes, so every thread issues the same number of VMEM ops per
 // stage and the counted wait is exact.
 //
+// csr_pm_steps_kernel: the same pipeline with eps >= 2 mixing steps per stage
+// (FedLCon's X <- W^eps X, DIST/simulators.py:190-196).  Steps 2 .. eps of a
+// coordinate need only its p-row, which is whole in LDS, so they run LDS to
+// LDS between the stage image and one scratch image and the bank still
+// crosses HBM once.  Geometry: up to 4096 agents 48 KiB x 2 + <= 48 KiB
+// scratch (the mix and all modes of the fused round); beyond, 32 KiB x 4 +
+// 32 KiB (all 160 KiB; the ring drops from five buffers to four).  Measured,
+// random 4-regular W, (a) eps single-step launches against (b) the fused pass
+// in one process on the same buffers (tools/pm_steps_ab.py,
+// profiles/pm_steps_ab.jsonl); HBM = 2 N P 4 bytes over (b) at 8 TB/s:
+//   1024 x 2^20  eps 2 / 3 / 5 / 8: (a) 3.29 / 4.94 / 8.22 / 13.15 ms,
+//                (b) 2.14 / 3.09 / 4.99 / 7.85 ms, (b)/(a) 0.65 / 0.62 / 0.61 / 0.60,
+//                HBM 50 / 35 / 22 / 14 %
+//   8192 x 2^20  (a) 24.26 / 35.90 / 60.13 / 96.83, (b) 19.91 / 27.74 / 43.41 / 66.98,
+//                (b)/(a) 0.82 / 0.77 / 0.72 / 0.69, HBM 43 / 31 / 20 / 13 %
+// An extra step is 0.95 ms at 1024 agents (LDS-bound: random-bank conflicts
+// and two barriers per step) and 7.8 ms at 8192.  Alternatives up to 4096
+// agents, eps 2 / 5 at 1024 x 2^20 (profiles/pm_steps_geom.txt): 48 KiB x 2 +
+// 48 KiB 2.15 / 5.01 ms; 64 KiB x 2 + 32 KiB scratch (sr cut to fit it) 2.37 /
+// 5.32; 32 KiB x 3 + 32 KiB 2.32 / 5.29 -- more p-rows per barrier won.  The
+// fused round, eps 5, 1024 x 2^20: least squares + momentum 6.73 ms against
+// 10.00 for four mixes and the round, logistic 6.73 against 8.74.
+//
 // Tried and retired (each was a launch variant behind an environment switch;
 // the code last existed in commit 2d96633):
 //  * DOL_PM_DGD_GEOM, the fused round's stage geometry forced to 64 KiB x 2,
@@ -154,20 +177,20 @@ struct PmDgd {
 
 // Mix one stage image (sr p-rows of xw floats at im0, p-rows p0 ..) and store
 // its rows of YT (and, OBJ >= 0, run the local steps first: target / momentum
-// images of nw floats per p-row follow the X image): spt (x2 with a momentum
+// images of nw floats per p-row at tim0, behind the stage's X image as it came
+// in -- which the multi-step kernel's im0 need not be): spt (x2 with a momentum
 // store) buffer stores per thread, out-of-range ones dropped.
 template <int T, int QPT, int OBJ = -1, int MODE = 0>
 __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __restrict__ im0, float* __restrict__ YT,
                                           int64_t ldy, int n_rows, int64_t P, int64_t p0, int xw, int sr, int spt,
                                           int q0, int g, int GR, const int32_t* __restrict__ rowptr,
                                           const int32_t* __restrict__ col, const float* __restrict__ val,
-                                          const PmDgd& e, int nw) {
+                                          const PmDgd& e, int nw, const float* __restrict__ tim0) {
   const int nq = (n_rows + 3) / 4;
   const int64_t rows_here = std::min<int64_t>(sr, P - p0);
   const rsrc_t ry = make_rsrc(YT + p0 * ldy, static_cast<uint32_t>(rows_here * ldy * 4));
   rsrc_t rm = ry;
   if constexpr (OBJ >= 0 && MODE != 0) rm = make_rsrc(e.M + p0 * e.ldm, static_cast<uint32_t>(rows_here * e.ldm * 4));
-  const float* tim0 = im0 + sr * xw;      // target images
   const float* mim0 = tim0 + sr * nw;     // momentum images (MODE 2)
   for (int u = 0; u < spt / QPT; ++u) {
     const int pr = g + u * GR;
@@ -218,6 +241,32 @@ __device__ __forceinline__ void mix_stage(const Quad (&Q)[QPT], const float* __r
   }
 }
 
+// One stage into the ring buffer at dst by LDS-DMA: the sr p-rows from p0 as
+// nX 16-B pieces of X images (xq per p-row, the first xr4 holding data), then
+// (OBJ >= 0) the target and (MODE 2) momentum images, nTM pieces each (nq4 per
+// p-row, nr4 holding data).  SF / 4 / T loads per thread, dead pieces
+// included, so the counted wait is the same for every thread.
+template <int T, int SF, int OBJ, int MODE>
+__device__ __forceinline__ void issue_stage(float* dst, const float* __restrict__ XT, int64_t ldx, int64_t P,
+                                            int64_t p0, int xq, int xr4, int nq4, int nr4, int nX, int nTM,
+                                            const PmDgd& e, int tid, int wave) {
+#pragma unroll
+  for (int d = 0; d < SF / 4 / T; ++d) {
+    const int pc = d * T + tid;
+    const float* src = XT;  // dead pieces re-read XT[0..3]
+    if (pc < nX) {
+      const int pr = pc / xq, j4 = pc - pr * xq;
+      if (p0 + pr < P && j4 < xr4) src = XT + (p0 + pr) * ldx + 4 * j4;
+    } else if (OBJ >= 0) {
+      const int pt = pc - nX, op = pt / nTM, r = pt - op * nTM;  // op 0: target, 1: momentum
+      const int pr = r / nq4, j4 = r - pr * nq4;
+      if ((op == 0 || (MODE == 2 && op == 1)) && p0 + pr < P && j4 < nr4)
+        src = op == 0 ? e.T + (p0 + pr) * e.ldt + 4 * j4 : e.M + (p0 + pr) * e.ldm + 4 * j4;
+    }
+    __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, kNT);
+  }
+}
+
 // T threads per workgroup, SF floats per stage buffer, NBUF buffers, QPT
 // quads per thread.
 // OBJ >= 0: the config-3 epilogue (PmDgd), its target (+ momentum) p-rows
@@ -262,23 +311,8 @@ __global__ __launch_bounds__(T) void csr_pm_kernel(const float* __restrict__ XT,
   const int nq4 = nw / 4, nr4 = (n_rows + 3) / 4;
   const int nX = sr * xq, nTM = sr * nq4;  // pieces of the X images, of one epilogue operand's images
   auto issue = [&](int64_t k) {      // stage k of this workgroup -> buffer k % NBUF
-    const int64_t p0 = stage_of(k) * sr;
-    float* dst = img + (k % NBUF) * SF;
-#pragma unroll
-    for (int d = 0; d < kDma; ++d) {
-      const int pc = d * T + tid;
-      const float* src = XT;  // dead pieces re-read XT[0..3]
-      if (pc < nX) {
-        const int pr = pc / xq, j4 = pc - pr * xq;
-        if (p0 + pr < P && j4 < xr4) src = XT + (p0 + pr) * ldx + 4 * j4;
-      } else if (OBJ >= 0) {
-        const int pt = pc - nX, op = pt / nTM, r = pt - op * nTM;  // op 0: target, 1: momentum
-        const int pr = r / nq4, j4 = r - pr * nq4;
-        if ((op == 0 || (MODE == 2 && op == 1)) && p0 + pr < P && j4 < nr4)
-          src = op == 0 ? e.T + (p0 + pr) * e.ldt + 4 * j4 : e.M + (p0 + pr) * e.ldm + 4 * j4;
-      }
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, kNT);
-    }
+    issue_stage<T, SF, OBJ, MODE>(img + (k % NBUF) * SF, XT, ldx, P, stage_of(k) * sr, xq, xr4, nq4, nr4, nX, nTM, e,
+                                  tid, wave);
   };
   constexpr int kStores = (OBJ >= 0 && MODE != 0) ? 2 : 1;  // buffer stores per (p-row, quad)
 #pragma unroll
@@ -298,8 +332,112 @@ __global__ __launch_bounds__(T) void csr_pm_kernel(const float* __restrict__ XT,
     if (k + NBUF - 1 < nk) issue(k + NBUF - 1);
     const int64_t p0 = stage_of(k) * sr;
     const float* im0 = img + (k % NBUF) * SF;
-    mix_stage<T, QPT, OBJ, MODE>(Q, im0, YT, ldy, n_rows, P, p0, xw, sr, spt, q0, g, GR, rowptr, col, val, e, nw);
+    mix_stage<T, QPT, OBJ, MODE>(Q, im0, YT, ldy, n_rows, P, p0, xw, sr, spt, q0, g, GR, rowptr, col, val, e, nw,
+                                 im0 + sr * xw);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this stage's LDS reads are done before the next barrier
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// One intermediate mixing step of a stage, LDS to LDS: the image at dst gets
+// W times the image at src for the stage's live p-rows (same layout, xw
+// floats per p-row), every thread writing the quads it owns as one 16-B LDS
+// store.  The ragged last quad writes its dead lanes (+0) too: they lie below
+// 4 * ceil(n / 4) <= xw and no gather reads them (col < n).  No vector-memory
+// operation except a long row's fallback loads, which mix_quad consumes at
+// once -- nothing is left in flight for the caller's counted wait.
+template <int T, int QPT>
+__device__ __forceinline__ void mix_image(const Quad (&Q)[QPT], const float* src, float* dst, int n_rows, int rows_here,
+                                          int xw, int spt, int q0, int g, int GR,
+                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                          const float* __restrict__ val) {
+  const int nq = (n_rows + 3) / 4;
+  for (int u = 0; u < spt / QPT; ++u) {
+    const int pr = g + u * GR;
+    if (pr >= rows_here) continue;
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      const int q = q0 + j * T;
+      if (q < nq) *reinterpret_cast<f4*>(dst + pr * xw + 4 * q) = mix_quad(Q[j], src + pr * xw, q, rowptr, col, val);
+    }
+  }
+}
+
+// csr_pm_kernel with mix_steps >= 2 mixing steps per stage (X <- W^k X, the
+// inner loop of FedLCon's round, DIST/simulators.py:190-196): a stage's p-rows
+// are complete in LDS, and step t + 1 of a coordinate needs nothing but step
+// t's p-row, so the bank still crosses HBM once.  Stage image A (ring buffer
+// k % NBUF) is mixed into one scratch image S behind the ring, S back into A,
+// and so on; the last step mixes from whichever holds step mix_steps - 1 and
+// stores from registers as mix_stage always does (the epilogue operands stay
+// where the DMA put them, behind A's X part).  Between steps: s_waitcnt
+// lgkmcnt(0) and a raw s_barrier, which order LDS against LDS only -- the
+// intermediate steps issue no vector-memory operation, so the ring's vmcnt
+// count is csr_pm_kernel's.  S is never a DMA target, and A's buffer is not
+// re-issued before the barrier that opens the next stage (as there).
+template <int T, int SF, int NBUF, int QPT, int OBJ = -1, int MODE = 0>
+__global__ __launch_bounds__(T) void csr_pm_steps_kernel(const float* __restrict__ XT, int64_t ldx,
+                                                         float* __restrict__ YT, int64_t ldy, int n_rows, int64_t P,
+                                                         int xw, int sr, int qp_log2, int spt, int64_t n_stages,
+                                                         int nseg, const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const float* __restrict__ val, PmDgd e, int nw,
+                                                         int mix_steps) {
+  constexpr int kDma = SF / 4 / T;
+  static_assert(kDma * 4 * T == SF, "a stage is a whole number of DMA rounds");
+  extern __shared__ __attribute__((aligned(16))) float img[];  // NBUF x SF, then the scratch image (sr * xw)
+  float* const scratch = img + NBUF * SF;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = QPT == 1 ? (tid & ((1 << qp_log2) - 1)) : tid;
+  const int g = QPT == 1 ? (tid >> qp_log2) : 0;
+  const int GR = QPT == 1 ? (T >> qp_log2) : 1;
+  const int nnz = rowptr[n_rows];
+  Quad Q[QPT];
+  if (nnz > 0) {
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) load_quad(Q[j], q0 + j * T, n_rows, nnz, rowptr, col, val);
+  } else {
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) Q[j] = Quad{};
+  }
+  // stage order and ring as csr_pm_kernel
+  const int64_t W = gridDim.x / nseg, seg = blockIdx.x % nseg, wl = blockIdx.x / nseg;
+  const int64_t seg_len = (n_stages + nseg - 1) / nseg;
+  const int64_t seg_n = std::max<int64_t>(0, std::min<int64_t>(seg_len, n_stages - seg * seg_len));
+  const int64_t nk = wl < seg_n ? (seg_n - wl + W - 1) / W : 0;
+  auto stage_of = [&](int64_t k) { return seg * seg_len + wl + k * W; };
+  const int xq = xw / 4, xr4 = (n_rows + 3) / 4;
+  const int nq4 = nw / 4, nr4 = (n_rows + 3) / 4;
+  const int nX = sr * xq, nTM = sr * nq4;
+  auto issue = [&](int64_t k) {
+    issue_stage<T, SF, OBJ, MODE>(img + (k % NBUF) * SF, XT, ldx, P, stage_of(k) * sr, xq, xr4, nq4, nr4, nX, nTM, e,
+                                  tid, wave);
+  };
+  constexpr int kStores = (OBJ >= 0 && MODE != 0) ? 2 : 1;
+#pragma unroll
+  for (int k = 0; k < NBUF - 1; ++k)
+    if (k < nk) issue(k);
+  for (int64_t k = 0; k < nk; ++k) {
+    const int64_t ahead = std::min<int64_t>(nk - 1, k + NBUF - 2) - k;
+    wait_vmcnt(static_cast<int>(std::min<int64_t>(63, kStores * spt * std::min<int64_t>(k, NBUF - 1) + kDma * ahead)));
+    __builtin_amdgcn_s_barrier();  // stage k landed; buffer (k-1) % NBUF and the scratch image are free
+    if (k + NBUF - 1 < nk) issue(k + NBUF - 1);
+    const int64_t p0 = stage_of(k) * sr;
+    float* const A = img + (k % NBUF) * SF;
+    const int rows_here = static_cast<int>(std::min<int64_t>(sr, P - p0));
+    float *cur = A, *nxt = scratch;
+    for (int t = 1; t < mix_steps; ++t) {
+      mix_image<T, QPT>(Q, cur, nxt, n_rows, rows_here, xw, spt, q0, g, GR, rowptr, col, val);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of cur and writes of nxt are done
+      __builtin_amdgcn_s_barrier();                       // ... and every wave's: nxt is whole, cur is free
+      float* const was = cur;
+      cur = nxt;
+      nxt = was;
+    }
+    mix_stage<T, QPT, OBJ, MODE>(Q, cur, YT, ldy, n_rows, P, p0, xw, sr, spt, q0, g, GR, rowptr, col, val, e, nw,
+                                 A + sr * xw);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -353,10 +491,15 @@ int dol_pm_set_stage_order(int32_t nseg) {
 
 namespace {
 
-// obj < 0: the plain mix; else the config-3 round (epilogue e, momentum mode)
+// obj < 0: the plain mix; else the config-3 round (epilogue e, momentum mode).
+// mix_steps > 1: W^mix_steps in one pass (csr_pm_steps_kernel; W square, the
+// callers pass x_rows == n_rows); 1 is the single-step kernel, launched as ever.
 int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows, float* YT, int64_t ldy,
                     int32_t n_rows, int64_t P, const int32_t* rowptr, const int32_t* col, const float* val, int obj,
-                    int mode, const PmDgd& e, int32_t nseg_req, hipStream_t s) {
+                    int mode, const PmDgd& e, int32_t nseg_req, hipStream_t s, int mix_steps = 1) {
+  if (mix_steps < 1 || mix_steps > DOL_PM_MAX_FUSED_STEPS)
+    return fail(DOL_EINVAL, "%s: %d mixing steps outside [1, %d] (the cap bounds one launch's run time)", nm,
+                mix_steps, DOL_PM_MAX_FUSED_STEPS);
   if (nseg_req < 0 || nseg_req > 256) return fail(DOL_EINVAL, "%s: stage order %d outside [0, 256]", nm, nseg_req);
   if (n_rows < 0 || x_rows < 0 || P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
   if (n_rows == 0 || P == 0) { dol::g_err[0] = '\0'; return DOL_OK; }
@@ -389,12 +532,18 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   // one stage per short-lived workgroup 4.4; a per-wave ring (no workgroup
   // barrier, 4 KiB p-rows, 176 VGPRs) 1.64.
   const bool big = nq > kT1 || xw > 4096;
+  const bool multi = mix_steps > 1;
   // fused round (<= 4096 agents): 64 KiB x 2 stages, or 80 KiB x 2 with the
   // momentum read (mode 2).  Beyond 4096 agents: five 32-KiB buffers (all 160
   // KiB, four p-rows in flight; profiles/r02_pm_nbuf.txt).  At <= 4096 agents
-  // 5 x 32 KiB ran level with 2 x 64 KiB (1.56-1.59 ms at 1024 x 2^20)
-  const int SF = big ? 8192 : (ne == 2 ? 20480 : 16384);
-  const int NB = big ? 5 : 2;  // must match the kernel's NBUF (LDS size)
+  // 5 x 32 KiB ran level with 2 x 64 KiB (1.56-1.59 ms at 1024 x 2^20).
+  // Multi-step (csr_pm_steps_kernel): the ring plus one scratch image of the
+  // stage's X part.  Up to 4096 agents 48 KiB x 2 + <= 48 KiB for the mix and
+  // every mode of the round (at 4096 agents with momentum: X, target and
+  // momentum p-row = one 48 KiB stage, 16 KiB scratch); beyond, 32 KiB x 4 +
+  // 32 KiB, the whole 160 KiB.
+  const int SF = multi ? (big ? 8192 : 12288) : big ? 8192 : (ne == 2 ? 20480 : 16384);
+  const int NB = multi ? (big ? 4 : 2) : big ? 5 : 2;  // must match the kernel's NBUF (LDS size)
   int sr = SF / (xw + ne * nw);
   int qp_log2 = 0, spt;
   if (!big) {
@@ -412,13 +561,30 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   const int64_t n_stages = (P + sr - 1) / sr;
   const int ncu = n_cus();
   if (ncu <= 0) return fail(DOL_EINVAL, "%s: no device", nm);
+  const int64_t grid = std::min<int64_t>(ncu, n_stages);
+  const int proc = g_pm_nseg.load(std::memory_order_relaxed);
+  int nseg = nseg_req > 0 ? nseg_req : proc > 0 ? proc : env_int("DOL_PM_NSEG", 8);
+  if (nseg < 1 || grid % nseg) nseg = 1;
+  auto go_steps = [&](auto kern) {
+    const int lds = (NB * SF + sr * xw) * 4;  // the ring, then the scratch image
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kT1), lds, s, XT, ldx, YT, ldy, n_rows, P, xw, sr,
+                       qp_log2, spt, n_stages, nseg, rowptr, col, val, e, nw, mix_steps);
+  };
+  if (multi) {
+    if (obj < 0) {
+      if (big) go_steps(csr_pm_steps_kernel<kT1, 8192, 4, 2>);
+      else go_steps(csr_pm_steps_kernel<kT1, 12288, 2, 1>);
+    } else {
+      dispatch([&](auto oc, auto mc) {
+        go_steps(csr_pm_steps_kernel<kT1, 12288, 2, 1, decltype(oc)::value, decltype(mc)::value>);
+      }, Ints<0, 1>{obj}, Ints<0, 1, 2>{mode});
+    }
+    return check_launch(nm);
+  }
   auto go = [&](auto kern) {
     const int lds = NB * SF * 4;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    const int64_t grid = std::min<int64_t>(ncu, n_stages);
-    const int proc = g_pm_nseg.load(std::memory_order_relaxed);
-    int nseg = nseg_req > 0 ? nseg_req : proc > 0 ? proc : env_int("DOL_PM_NSEG", 8);
-    if (nseg < 1 || grid % nseg) nseg = 1;
     static const int wait_mode = env_int("DOL_PM_WAIT", 1);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kT1), lds, s, XT, ldx, x_rows, YT, ldy, n_rows, P,
                        xw, sr, qp_log2, spt, n_stages, nseg, rowptr, col, val, e, nw, wait_mode);
@@ -471,6 +637,42 @@ int dol_dgd_csr_pm_ex_f32(const float* XT, int64_t ldx, int32_t x_rows, float* Y
   const int mode = momentum_mode(momentum, first_step);
   const PmDgd e{TT, ldt, mode ? MT : nullptr, mode ? ldm : 0, -lr, momentum, local_steps};
   return mix_csr_pm_impl(nm, XT, ldx, x_rows, YT, ldy, n_rows, P, rowptr, col, val, objective, mode, e, nseg, s);
+}
+
+int dol_mix_csr_pm_steps_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                             const int32_t* rowptr, const int32_t* col, const float* val, int32_t steps,
+                             hipStream_t s) {
+  return dol_mix_csr_pm_steps_ex_f32(XT, ldx, YT, ldy, n, P, rowptr, col, val, steps, 0, s);
+}
+
+int dol_mix_csr_pm_steps_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                                const int32_t* rowptr, const int32_t* col, const float* val, int32_t steps,
+                                int32_t nseg, hipStream_t s) {
+  DOL_DIMS_OK("dol_mix_csr_pm_steps_f32", ldx, ldy, P);
+  return mix_csr_pm_impl("dol_mix_csr_pm_steps_f32", XT, ldx, n, YT, ldy, n, P, rowptr, col, val, -1, 0, PmDgd{}, nseg,
+                         s, steps);
+}
+
+int dol_dgd_csr_pm_steps_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                             const int32_t* rowptr, const int32_t* col, const float* val, const float* TT,
+                             int64_t ldt, float* MT, int64_t ldm, int32_t objective, int32_t mix_steps,
+                             int32_t local_steps, float lr, float momentum, int first_step, hipStream_t s) {
+  return dol_dgd_csr_pm_steps_ex_f32(XT, ldx, YT, ldy, n, P, rowptr, col, val, TT, ldt, MT, ldm, objective, mix_steps,
+                                     local_steps, lr, momentum, first_step, 0, s);
+}
+
+int dol_dgd_csr_pm_steps_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                                const int32_t* rowptr, const int32_t* col, const float* val, const float* TT,
+                                int64_t ldt, float* MT, int64_t ldm, int32_t objective, int32_t mix_steps,
+                                int32_t local_steps, float lr, float momentum, int first_step, int32_t nseg,
+                                hipStream_t s) {
+  DOL_DIMS_OK("dol_dgd_csr_pm_steps_f32", ldx, ldy, P, ldt, ldm);
+  const char* nm = "dol_dgd_csr_pm_steps_f32";
+  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
+  if (local_steps < 1) return fail(DOL_EINVAL, "%s: local_steps must be >= 1", nm);
+  const int mode = momentum_mode(momentum, first_step);
+  const PmDgd e{TT, ldt, mode ? MT : nullptr, mode ? ldm : 0, -lr, momentum, local_steps};
+  return mix_csr_pm_impl(nm, XT, ldx, n, YT, ldy, n, P, rowptr, col, val, objective, mode, e, nseg, s, mix_steps);
 }
 
 int dol_transpose_f32(const float* A, int64_t lda, float* B, int64_t ldb, int64_t rows, int64_t cols, hipStream_t s) {

@@ -467,7 +467,10 @@ class MixingPlan:
     def apply_steps(self, X: torch.Tensor, Y: torch.Tensor, steps: int, P: Optional[int] = None) -> int:
         """Apply up to `steps` synchronous rounds in one pass when the plan and
         layout allow (ring, P % 4 == 0, 16-B aligned rows); returns how many
-        rounds were applied (>= 1).  Bit-identical to single rounds."""
+        rounds were applied (>= 1).  Bit-identical to single rounds.  A sparse
+        W on this agent-major layout is one round per call; on the
+        parameter-major bank ops.mix_csr_pm_steps fuses the steps for any
+        sparse W (SeparableDGDPM.mix / consensus_steps)."""
         P = X.shape[1] if P is None else P
         self._check_x(X)
         k = min(int(steps), self.MAX_FUSED_STEPS)

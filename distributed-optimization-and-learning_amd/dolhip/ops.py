@@ -30,11 +30,12 @@ __all__ = [
     "transpose", "PM_MAX_AGENTS", "stream_copy_rows", "dgd_csr_pm", "PM_DGD_MAX_AGENTS",
     "SLAB_CHUNK", "SLAB_ROWS", "csr_slab_pack", "mix_csr_slab", "slab_layout_ok", "dense_to_csr",
     "admm_ls_round_mean", "slab_variant", "SLAB_VARIANTS", "SPLIT3_FUSE_MAX_M", "SPLIT3_W_READY",
-    "SPLIT3_X_ROWS_PADDED", "SPLIT3_FUSE_X", "AUTOTUNE_MIN_BYTES", "AUTOTUNE_REPS",
+    "SPLIT3_X_ROWS_PADDED", "SPLIT3_FUSE_X", "AUTOTUNE_MIN_BYTES", "AUTOTUNE_REPS", "PM_MAX_FUSED_STEPS",
 ]
 
 PM_MAX_AGENTS = 8192  # dol_mix_csr_pm_f32: one p-row image (<= 32 KiB) per LDS stage
 PM_DGD_MAX_AGENTS = 4096  # dol_dgd_csr_pm_f32: X, target and momentum p-rows share a 64 KiB stage
+PM_MAX_FUSED_STEPS = 64  # DOL_PM_MAX_FUSED_STEPS: mixing steps in one dol_mix_csr_pm_steps_f32 launch
 RING_STEPS_VARIANTS = (1, 2, 3, 4, 5)
 PM_STAGE_ORDERS = (8, 16, 32)
 AUTOTUNE_MIN_BYTES = 1 << 30  # below this one pass is too short to be worth timing
@@ -1010,3 +1011,10 @@ def mlp_step(w: torch.Tensor, X: torch.Tensor, y: torch.Tensor, d: int, h: int, 
                  y.stride(0) if n > 1 else B, _ptr(loss), n, B, d, h, c, float(lr), float(momentum), float(rho),
                  int(bool(first_step)), int(bool(update)), work.data_ptr(), _stream(w))
     return loss
+
+
+# ---------------------------------------------------------------------------
+# Multi-step consensus on the parameter-major bank (pm_steps.py, which builds
+# on the validators above): mix_csr_pm_steps, dgd_csr_pm_steps.
+# ---------------------------------------------------------------------------
+from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noqa: E402,F401

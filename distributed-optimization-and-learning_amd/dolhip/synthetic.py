@@ -398,11 +398,18 @@ class SeparableDGDPM:
     (dol_dgd_csr_pm_f32).  Build it from a SeparableDGD
     (`from_agent_major`, which transposes that problem's current state) or
     fresh (random init drawn directly in this layout).  At most
-    ops.PM_DGD_MAX_AGENTS agents."""
+    ops.PM_DGD_MAX_AGENTS agents.  consensus_steps = k > 1 makes the round
+    FedLCon's (DIST/simulators.py:190-196): X <- W^k X, then the local steps,
+    still one kernel and one pass over the bank (dol_dgd_csr_pm_steps_f32; W
+    must be square); 1 is the round above, through the same call as ever."""
 
     def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
-                 momentum: float = 0.0, local_steps: int = 1, seed: int = 2028, _state=None):
+                 momentum: float = 0.0, local_steps: int = 1, seed: int = 2028, _state=None,
+                 consensus_steps: int = 1):
         from . import ops
+        if int(consensus_steps) < 1:
+            raise ValueError("consensus_steps must be >= 1")
+        self.consensus_steps = int(consensus_steps)
         if plan.n_rows > ops.PM_DGD_MAX_AGENTS:
             raise ValueError(f"the parameter-major round takes at most {ops.PM_DGD_MAX_AGENTS} agents")
         if plan.kind == "dense":
@@ -427,10 +434,11 @@ class SeparableDGDPM:
                 t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
 
     @classmethod
-    def from_agent_major(cls, prob: "SeparableDGD") -> "SeparableDGDPM":
+    def from_agent_major(cls, prob: "SeparableDGD", consensus_steps: int = 1) -> "SeparableDGDPM":
         """Transpose prob's current state (x, targets, momentum, first-step flag)."""
         from . import ops
-        self = cls(prob.plan, prob.P, prob.objective, prob.lr, prob.mu, prob.local_steps, _state=True)
+        self = cls(prob.plan, prob.P, prob.objective, prob.lr, prob.mu, prob.local_steps, _state=True,
+                   consensus_steps=consensus_steps)
         ops.transpose(prob.params(), self.XT, prob.plan.n_rows, prob.P)
         ops.transpose(prob.targets(), self.TT, prob.plan.n_rows, prob.P)
         if self.MT is not None:
@@ -439,14 +447,32 @@ class SeparableDGDPM:
         return self
 
     def round(self) -> None:
-        """X <- W X, then the local steps (one kernel); swaps XT / YT."""
+        """X <- W^consensus_steps X, then the local steps (one kernel); swaps XT / YT."""
         from . import ops
         p = self.plan
-        ops.dgd_csr_pm(self.XT, self.YT, p.rowptr, p.col, p.val, self.TT, self.MT, objective=self.objective,
-                       steps=self.local_steps, lr=self.lr, momentum=self.mu, first_step=self.first, P=self.P)
-        self.XT, self.YT = self.YT, self.XT
+        if self.consensus_steps == 1:
+            ops.dgd_csr_pm(self.XT, self.YT, p.rowptr, p.col, p.val, self.TT, self.MT, objective=self.objective,
+                           steps=self.local_steps, lr=self.lr, momentum=self.mu, first_step=self.first, P=self.P)
+            self.XT, self.YT = self.YT, self.XT
+        else:
+            self._keep(ops.dgd_csr_pm_steps(self.XT, self.YT, p.rowptr, p.col, p.val, self.TT, self.MT,
+                                            objective=self.objective, mix_steps=self.consensus_steps,
+                                            steps=self.local_steps, lr=self.lr, momentum=self.mu,
+                                            first_step=self.first, P=self.P))
         self.first = False
         self.rounds += 1
+
+    def mix(self, steps: int = 1) -> None:
+        """X <- W^steps X, plain consensus with no local step: the inner loop of
+        FedLCon.run on this bank, one pass per ops.PM_MAX_FUSED_STEPS steps."""
+        from . import ops
+        p = self.plan
+        self._keep(ops.mix_csr_pm_steps(self.XT, self.YT, p.rowptr, p.col, p.val, steps, P=self.P))
+
+    def _keep(self, holder: torch.Tensor) -> None:
+        """Make the buffer a multi-pass call left its result in the current XT."""
+        if holder is self.YT:
+            self.XT, self.YT = self.YT, self.XT
 
     def params(self) -> torch.Tensor:
         """Agent-major copy [N, P] of the current parameters (diagnostic)."""

@@ -82,6 +82,27 @@ int dol_mix_csr_pm_ex_f32(const float* XT, int64_t ldx, int32_t x_rows, float* Y
                           hipStream_t s);
 
 /*
+ * `steps` synchronous mixing rounds on the parameter-major bank in one HBM
+ * pass: YT = W^steps XT, the inner loop of FedLCon's round
+ * (DIST/simulators.py:190-196, each step the consensus of
+ * DIST/clients.py:61-69), bit-identical to `steps` dol_mix_csr_pm_f32 calls.
+ * A p-row is one coordinate's whole mixing problem and sits complete in LDS,
+ * so steps 2 .. steps run LDS to LDS and X and Y still stream once, for any
+ * sparse W.  W is square: n is both the agent count of XT and of YT, and
+ * 0 <= col < n.  steps in [1, DOL_PM_MAX_FUSED_STEPS] (the cap bounds one
+ * launch's run time; above it DOL_EINVAL, and callers chain passes); steps ==
+ * 1 is dol_mix_csr_pm_f32.  Every other limit as dol_mix_csr_pm_f32.
+ */
+#define DOL_PM_MAX_FUSED_STEPS 64
+int dol_mix_csr_pm_steps_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                             const int32_t* rowptr, const int32_t* col, const float* val, int32_t steps,
+                             hipStream_t s);
+/* The same call with the stage order given per call (see dol_mix_csr_pm_ex_f32). */
+int dol_mix_csr_pm_steps_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                                const int32_t* rowptr, const int32_t* col, const float* val, int32_t steps,
+                                int32_t nseg, hipStream_t s);
+
+/*
  * Stage order of the parameter-major kernels (dol_mix_csr_pm_f32,
  * dol_dgd_csr_pm_f32) for this process: the P range is streamed as `nseg`
  * separate regions at once (a divisor of the CU count; others fall back to 1).
@@ -308,6 +329,25 @@ int dol_dgd_csr_pm_ex_f32(const float* XT, int64_t ldx, int32_t x_rows, float* Y
                           int64_t P, const int32_t* rowptr, const int32_t* col, const float* val, const float* TT,
                           int64_t ldt, float* MT, int64_t ldm, int32_t objective, int32_t local_steps, float lr,
                           float momentum, int first_step, int32_t nseg, hipStream_t s);
+/*
+ * FedLCon's whole round on the parameter-major bank in one pass
+ * (DIST/simulators.py:190-196 + DIST/clients.py:61-69): mix_steps mixing
+ * rounds as dol_mix_csr_pm_steps_f32 (W square, mix_steps in [1,
+ * DOL_PM_MAX_FUSED_STEPS]), then the local steps of dol_dgd_csr_pm_f32 on the
+ * result; bit-identical to mix_steps - 1 dol_mix_csr_pm_f32 calls and one
+ * dol_dgd_csr_pm_f32.  Limits as dol_dgd_csr_pm_f32 (n <= 4096); mix_steps ==
+ * 1 is that call.
+ */
+int dol_dgd_csr_pm_steps_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                             const int32_t* rowptr, const int32_t* col, const float* val, const float* TT,
+                             int64_t ldt, float* MT, int64_t ldm, int32_t objective, int32_t mix_steps,
+                             int32_t local_steps, float lr, float momentum, int first_step, hipStream_t s);
+/* dol_dgd_csr_pm_steps_f32 with the stage order per call (see dol_mix_csr_pm_ex_f32). */
+int dol_dgd_csr_pm_steps_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                                const int32_t* rowptr, const int32_t* col, const float* val, const float* TT,
+                                int64_t ldt, float* MT, int64_t ldm, int32_t objective, int32_t mix_steps,
+                                int32_t local_steps, float lr, float momentum, int first_step, int32_t nseg,
+                                hipStream_t s);
 
 /*
  * Fused local step of n_agents agents (rows of w/buf/g), replacing:
