@@ -1,7 +1,8 @@
 // admm.hip — the primal/dual family on the agent-major bank: the fused prox /
 // ADMM gradient term + momentum SGD step, the dual update and its residuals,
-// the FedADMM least-squares client round (alone, and fused with the server's
-// ordered mean) and the ordered sum / mean.
+// the least-squares client round of FedAvg / FedProx / FedADMM (one TERMS
+// selector; alone, and fused with the server's ordered mean) and the ordered
+// sum / mean.
 //
 // Dropped launch variant (the default's bits; code last present at 1a824fc):
 //   DOL_ADMM_ROUND_THREADS: admm_ls_round_mean_kernel strips forced to 1024 / 256 / 64 lanes; at 8192 x 2^17
@@ -205,14 +206,22 @@ __global__ __launch_bounds__(kThreads) void resid_reduce_kernel(const double* __
 // RESID: fp64 per-block partials of ||w - theta||^2 and ||alpha||^2 (fixed
 // reduction tree, deterministic), as admm_dual_kernel.
 // ----------------------------------------------------------------------------
-template <bool MOM>
+// TERMS selects the algorithm's gradient term (DOL_FED_AVG / _PROX / _ADMM), the
+// three of one Server.run (DEC/servers.py:50-81):
+//   0 FedAvg   g' = g                                  (DEC/clients.py:85-95)
+//   1 FedProx  g' = fl(g + fl(rho * fl(w - theta)))    (:101-115)
+//   2 FedADMM  the above, dual ascent included          (:125-144)
+// update_duals is a no-op for 0 and 1 (:58-59): a and ra are then not touched.
+template <bool MOM, int TERMS = 2>
 __device__ __forceinline__ void admm_ls_lane(float& w, float& b, float& a, float t, float th, float rho,
                                              float neg_lr, float mom, int steps, bool first, double& rw,
                                              double& ra) {
   w = th;
   for (int k = 0; k < steps; ++k) {
     const float g = w - t;
-    const float gg = g + (a + rho * (w - th));
+    float gg = g;
+    if constexpr (TERMS == 2) gg = g + (a + rho * (w - th));
+    if constexpr (TERMS == 1) gg = g + rho * (w - th);
     float d = gg;
     if constexpr (MOM) {
       b = (first && k == 0) ? gg : b * mom + gg;
@@ -221,11 +230,11 @@ __device__ __forceinline__ void admm_ls_lane(float& w, float& b, float& a, float
     w = __builtin_fmaf(neg_lr, d, w);
   }
   const float dl = w - th;
-  a = a + rho * dl;
+  if constexpr (TERMS == 2) a = a + rho * dl;
   // the product of two floats is exact in double, so fma == the reference's
   // separately rounded rw + d*d, one instruction fewer
   rw = __builtin_fma(double(dl), double(dl), rw);
-  ra = __builtin_fma(double(a), double(a), ra);
+  if constexpr (TERMS == 2) ra = __builtin_fma(double(a), double(a), ra);
 }
 
 // The same lane on two columns at once: packed fp32 (v_pk_add / v_pk_mul /
@@ -233,14 +242,16 @@ __device__ __forceinline__ void admm_ls_lane(float& w, float& b, float& a, float
 // element as admm_ls_lane.  At 10 local steps the round runs ~70 fp32 ops per
 // element: unpacked that is ~60 % of the HBM time in VALU issue.
 typedef float f2 __attribute__((ext_vector_type(2)));
-template <bool MOM>
+template <bool MOM, int TERMS = 2>
 __device__ __forceinline__ void admm_ls_lane2(f2& w, f2& b, f2& a, f2 t, f2 th, float rho, float neg_lr, float mom,
                                               int steps, bool first, double& rw, double& ra) {
   const f2 rho2 = {rho, rho}, nlr2 = {neg_lr, neg_lr}, mom2 = {mom, mom};
   w = th;
   for (int k = 0; k < steps; ++k) {
     const f2 g = w - t;
-    const f2 gg = g + (a + rho2 * (w - th));
+    f2 gg = g;
+    if constexpr (TERMS == 2) gg = g + (a + rho2 * (w - th));
+    if constexpr (TERMS == 1) gg = g + rho2 * (w - th);
     f2 d = gg;
     if constexpr (MOM) {
       b = (first && k == 0) ? gg : b * mom2 + gg;
@@ -249,25 +260,29 @@ __device__ __forceinline__ void admm_ls_lane2(f2& w, f2& b, f2& a, f2 t, f2 th, 
     w = __builtin_elementwise_fma(nlr2, d, w);
   }
   const f2 dl = w - th;
-  a = a + rho2 * dl;
+  if constexpr (TERMS == 2) a = a + rho2 * dl;
   rw = __builtin_fma(double(dl.x), double(dl.x), rw);
   rw = __builtin_fma(double(dl.y), double(dl.y), rw);
-  ra = __builtin_fma(double(a.x), double(a.x), ra);
-  ra = __builtin_fma(double(a.y), double(a.y), ra);
+  if constexpr (TERMS == 2) {
+    ra = __builtin_fma(double(a.x), double(a.x), ra);
+    ra = __builtin_fma(double(a.y), double(a.y), ra);
+  }
 }
 // f4 = two packed halves
-template <bool MOM>
+template <bool MOM, int TERMS = 2>
 __device__ __forceinline__ void admm_ls_lane4(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
                                               int steps, bool first, double& rw, double& ra) {
   f2 w0, w1, b0 = b.xy, b1 = b.zw, a0 = a.xy, a1 = a.zw;
-  admm_ls_lane2<MOM>(w0, b0, a0, t.xy, th.xy, rho, neg_lr, mom, steps, first, rw, ra);
-  admm_ls_lane2<MOM>(w1, b1, a1, t.zw, th.zw, rho, neg_lr, mom, steps, first, rw, ra);
+  admm_ls_lane2<MOM, TERMS>(w0, b0, a0, t.xy, th.xy, rho, neg_lr, mom, steps, first, rw, ra);
+  admm_ls_lane2<MOM, TERMS>(w1, b1, a1, t.zw, th.zw, rho, neg_lr, mom, steps, first, rw, ra);
   w = f4{w0.x, w0.y, w1.x, w1.y};
   b = f4{b0.x, b0.y, b1.x, b1.y};
   a = f4{a0.x, a0.y, a1.x, a1.y};
 }
 
-template <bool VEC, bool MOM, bool RESID>
+// TERMS < 2 (FedAvg / FedProx): A is NULL, no dual row is read or written and
+// no ||alpha||^2 partial is stored.
+template <bool VEC, bool MOM, bool RESID, int TERMS = 2>
 __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
     float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ A, int64_t lda,
     const float* __restrict__ T, int64_t ldt, const float* __restrict__ theta, const int32_t* __restrict__ agents,
@@ -285,14 +300,16 @@ __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
   const bool fst = first ? first[k] != 0 : false;
   float* wr = W + a_row * ldw;
   float* br = B + a_row * ldb;
-  float* ar = A + a_row * lda;
+  constexpr bool DUAL = TERMS == 2;
+  float* ar = DUAL ? A + a_row * lda : nullptr;
   const float* tr = T + a_row * ldt;
   double rw = 0.0, ra = 0.0;
   auto one = [&](int64_t c) {
-    float w, b = MOM ? br[c] : 0.0f, a = ar[c];
-    admm_ls_lane<MOM>(w, b, a, tr[c], theta[c], rho, neg_lr, mom, steps, fst, rw, ra);
+    float w, b = MOM ? br[c] : 0.0f, a = 0.0f;
+    if constexpr (DUAL) a = ar[c];
+    admm_ls_lane<MOM, TERMS>(w, b, a, tr[c], theta[c], rho, neg_lr, mom, steps, fst, rw, ra);
     wr[c] = w;
-    ar[c] = a;
+    if constexpr (DUAL) ar[c] = a;
     if constexpr (MOM) br[c] = b;
   };
   if constexpr (VEC) {
@@ -303,12 +320,13 @@ __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
       if (c < n4) {
         const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(tr) + c);
         const f4 th = reinterpret_cast<const f4*>(theta)[c];
-        f4 a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ar) + c);
+        f4 a = f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (DUAL) a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ar) + c);
         f4 b = MOM ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(br) + c) : f4{0.f, 0.f, 0.f, 0.f};
         f4 w;
-        admm_ls_lane4<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, fst, rw, ra);
+        admm_ls_lane4<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, fst, rw, ra);
         __builtin_nontemporal_store(w, reinterpret_cast<f4*>(wr) + c);
-        __builtin_nontemporal_store(a, reinterpret_cast<f4*>(ar) + c);
+        if constexpr (DUAL) __builtin_nontemporal_store(a, reinterpret_cast<f4*>(ar) + c);
         if constexpr (MOM) __builtin_nontemporal_store(b, reinterpret_cast<f4*>(br) + c);
       }
     }
@@ -323,11 +341,14 @@ __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
   }
   if constexpr (RESID) {
     const double sw = block_sum_f64(rw, smem);
-    __syncthreads();
-    const double sa = block_sum_f64(ra, smem);
+    double sa = 0.0;
+    if constexpr (DUAL) {
+      __syncthreads();
+      sa = block_sum_f64(ra, smem);
+    }
     if (threadIdx.x == 0) {
       partial[k * n_chunks + chunk] = sw;
-      partial[(gridDim.x / n_chunks + k) * n_chunks + chunk] = sa;
+      if constexpr (DUAL) partial[(gridDim.x / n_chunks + k) * n_chunks + chunk] = sa;
     }
   }
 }
@@ -388,17 +409,17 @@ __global__ __launch_bounds__(kThreads) void ordered_sum_kernel(
 // ----------------------------------------------------------------------------
 constexpr int kRoundPF = 3;
 
-template <bool MOM>
+template <bool MOM, int TERMS>
 __device__ __forceinline__ void admm_ls_lane_v(float& w, float& b, float& a, float t, float th, float rho, float neg_lr,
                                                float mom, int steps, bool first, double& rw, double& ra) {
-  admm_ls_lane<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
+  admm_ls_lane<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
 }
 // packed (measured at 8192 x 2^20, 10 steps: 34.6-35.1 ms vs 36.0-36.5 with
 // the per-element scalar form, profiles/r05zw_admm_round_ab.jsonl)
-template <bool MOM>
+template <bool MOM, int TERMS>
 __device__ __forceinline__ void admm_ls_lane_v(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
                                                int steps, bool first, double& rw, double& ra) {
-  admm_ls_lane4<MOM>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
+  admm_ls_lane4<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
 }
 __device__ __forceinline__ float ldnt(const float* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ f4 ldnt(const f4* p) { return __builtin_nontemporal_load(p); }
@@ -427,7 +448,21 @@ __device__ __forceinline__ double block_sum_f64_nt(double v, double* smem) {
   return s;
 }
 
-template <typename V, bool MOM, bool RESID, int NT, int PF = kRoundPF>
+// One prefetch group of the one-pass round: PF agents' target, dual and
+// momentum rows in flight per lane.  Without duals (FedAvg / FedProx) it
+// carries no a[].
+template <typename V, int PF, bool DUAL> struct RoundGrp {
+  V t[PF], a[PF], b[PF];
+  int64_t row[PF];
+};
+template <typename V, int PF> struct RoundGrp<V, PF, false> {
+  V t[PF], b[PF];
+  int64_t row[PF];
+};
+
+// TERMS < 2 (FedAvg / FedProx): A is NULL; the group carries no dual rows, no
+// dual row is loaded or stored and no ||alpha||^2 partial is written.
+template <typename V, bool MOM, bool RESID, int NT, int TERMS = 2, int PF = kRoundPF>
 __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
     float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ A, int64_t lda,
     const float* __restrict__ T, int64_t ldt, const float* __restrict__ theta, const int32_t* __restrict__ agents,
@@ -457,26 +492,25 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
   const V th = *cptr(theta, 0, 0);
   V acc = vzero(th);
   double rw = 0.0, ra = 0.0;
-  struct Grp {
-    V t[PF], a[PF], b[PF];
-    int64_t row[PF];
-  };
+  constexpr bool DUAL = TERMS == 2;
+  using Grp = RoundGrp<V, PF, DUAL>;
   auto load = [&](Grp& g, int k0) {  // agents k0 .. k0 + PF - 1, unconditionally (rows clamped)
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       g.row[u] = row_of(k0 + u);
       g.t[u] = ldnt(cptr(T, ldt, g.row[u]));
-      g.a[u] = ldnt(cptr(A, lda, g.row[u]));
+      if constexpr (DUAL) g.a[u] = ldnt(cptr(A, lda, g.row[u]));
       if constexpr (MOM) g.b[u] = ldnt(cptr(B, ldb, g.row[u]));
     }
   };
   auto run = [&](Grp& g, int u, int k) {  // agent k = group slot u: its steps, stores, and the chain
     const bool fst = first ? first[k] != 0 : false;
-    V w, bu = MOM ? g.b[u] : vzero(th), au = g.a[u];
+    V w, bu = MOM ? g.b[u] : vzero(th), au = vzero(th);
+    if constexpr (DUAL) au = g.a[u];
     double rwu = 0.0, rau = 0.0;
-    admm_ls_lane_v<MOM>(w, bu, au, g.t[u], th, rho, neg_lr, mom, steps, fst, rwu, rau);
+    admm_ls_lane_v<MOM, TERMS>(w, bu, au, g.t[u], th, rho, neg_lr, mom, steps, fst, rwu, rau);
     st(w, W, ldw, g.row[u]);
-    st(au, A, lda, g.row[u]);
+    if constexpr (DUAL) st(au, A, lda, g.row[u]);
     if constexpr (MOM) st(bu, B, ldb, g.row[u]);
     rw += live ? rwu : 0.0;
     ra += live ? rau : 0.0;
@@ -502,13 +536,126 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
   }
   if constexpr (RESID) {
     const double sw = block_sum_f64_nt<NT>(rw, smem);
-    __syncthreads();
-    const double sa = block_sum_f64_nt<NT>(ra, smem);
+    double sa = 0.0;
+    if constexpr (DUAL) {
+      __syncthreads();
+      sa = block_sum_f64_nt<NT>(ra, smem);
+    }
     if (threadIdx.x == 0) {
       partial[part_off + blockIdx.x] = sw;
-      partial[part_stride + part_off + blockIdx.x] = sa;
+      if constexpr (DUAL) partial[part_stride + part_off + blockIdx.x] = sa;
     }
   }
+}
+
+// The least-squares client round of the three algorithms; nm names the entry
+// point in the messages.  alg == DOL_FED_ADMM is dol_admm_ls_round_f32 as ever.
+int fed_ls_round(const char* nm, float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                 const float* target, int64_t ldt, const float* theta, const int32_t* agents, const int32_t* first,
+                 int32_t m, int64_t P, int32_t alg, float rho, float lr, float momentum, int32_t local_steps,
+                 double* resid_sq, double* alpha_sq, void* work, hipStream_t s) {
+  if (alg < DOL_FED_AVG || alg > DOL_FED_ADMM) return fail(DOL_EINVAL, "%s: algorithm must be 0 (FedAvg), 1 (FedProx) or 2 (FedADMM)", nm);
+  const bool dual = alg == DOL_FED_ADMM;
+  if (!dual) {
+    if (alpha) return fail(DOL_EINVAL, "%s: FedAvg / FedProx have no duals (alpha must be NULL)", nm);
+    if (alpha_sq) return fail(DOL_EINVAL, "%s: FedAvg / FedProx have no duals (alpha_sq must be NULL)", nm);
+    lda = 0;
+  }
+  DOL_DIMS_OK(nm, ldw, ldb, lda, ldt, P);
+  const bool mom = momentum != 0.0f;
+  DOL_CHECKED(check_rows(nm, m < 0 || P < 0 || local_steps < 0, m == 0,
+                         P > 0 && (!w || (dual && !alpha) || !target || !theta || (mom && !buf)), false, false));
+  if (dual && (resid_sq == nullptr) != (alpha_sq == nullptr)) return fail(DOL_EINVAL, "%s: pass both residual outputs or neither", nm);
+  if (resid_sq && !work && P > 0) return fail(DOL_EINVAL, "%s: residuals need a workspace", nm);
+  if (ldw < P || (dual && lda < P) || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P == 0) {
+    if (resid_sq) (void)hipMemsetAsync(resid_sq, 0, sizeof(double) * m, s);
+    if (alpha_sq) (void)hipMemsetAsync(alpha_sq, 0, sizeof(double) * m, s);
+    return check_launch(nm);
+  }
+  const bool vec = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
+                   (!mom || row_vec_ok(buf, ldb));
+  const int64_t per_block = int64_t(kThreads) * kDualIters;
+  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
+  if (mul_sat(chunks, m) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large", nm);
+  double* partial = static_cast<double*>(work);
+  const dim3 grid(static_cast<unsigned>(chunks * m));
+  dispatch([&](auto vc, auto mc, auto rc, auto tc) {
+    hipLaunchKernelGGL((admm_ls_round_kernel<decltype(vc)::value, decltype(mc)::value, decltype(rc)::value,
+                                             decltype(tc)::value>),
+                       grid, dim3(kThreads), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents, first, P,
+                       rho, -lr, momentum, local_steps, chunks, partial);
+  }, Bool{vec}, Bool{mom}, Bool{resid_sq != nullptr}, Ints<0, 1, 2>{alg});
+  if (resid_sq) hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial, chunks, resid_sq);
+  if (alpha_sq)
+    hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial + int64_t(m) * chunks, chunks,
+                       alpha_sq);
+  return check_launch(nm);
+}
+
+// The same fused with the server's ordered average (dol_admm_ls_round_mean_f32 for alg == DOL_FED_ADMM).
+int fed_ls_round_mean(const char* nm, float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                      const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                      const int32_t* first, int32_t m, int64_t P, int32_t alg, float rho, float lr, float momentum,
+                      int32_t local_steps, float* theta_out, float scale, double* resid_total, void* work,
+                      hipStream_t s) {
+  if (alg < DOL_FED_AVG || alg > DOL_FED_ADMM) return fail(DOL_EINVAL, "%s: algorithm must be 0 (FedAvg), 1 (FedProx) or 2 (FedADMM)", nm);
+  const bool dual = alg == DOL_FED_ADMM;
+  if (!dual) {
+    if (alpha) return fail(DOL_EINVAL, "%s: FedAvg / FedProx have no duals (alpha must be NULL)", nm);
+    lda = 0;
+  }
+  DOL_DIMS_OK(nm, ldw, ldb, lda, ldt, P);
+  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the average indexes w[0])", nm);
+  if (P < 0 || local_steps < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (!(scale > 0.0f)) return fail(DOL_EINVAL, "%s: scale must be > 0", nm);
+  const bool mom = momentum != 0.0f;
+  if (P > 0 && (!w || (dual && !alpha) || !target || !theta || !theta_out || (mom && !buf)))
+    return fail(DOL_EINVAL, "%s: null pointer", nm);
+  if (theta_out == w || (dual && theta_out == alpha) || theta_out == target || (mom && theta_out == buf))
+    return fail(DOL_EINVAL, "%s: theta_out aliases the rows", nm);
+  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
+  if (ldw < P || (dual && lda < P) || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  if (P == 0) {
+    if (resid_total) (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
+    return check_launch(nm);
+  }
+  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) &&
+                      row_vec_ok(theta, 0) && row_vec_ok(theta_out, 0) && (!mom || row_vec_ok(buf, ldb));
+  const ColSplit cs = split_cols(P, vec_ok);
+  // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
+  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
+  // lanes per CU) take 256-lane strips: the strips are the only parallelism
+  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
+  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
+  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
+  // for the two-kernel round (row-major client round + ordered sum), which
+  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
+  const int n_cu = n_cus() > 0 ? n_cus() : 256;
+  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
+  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
+  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
+  const int64_t nb = nb4 + nbt;
+  double* partial = static_cast<double*>(work);
+  const int do_div = scale != 1.0f;
+  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
+    dispatch([&](auto mc, auto rc, auto ntc, auto tc) {
+      hipLaunchKernelGGL((admm_ls_round_mean_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
+                                                    decltype(ntc)::value, decltype(tc)::value>),
+                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt,
+                         theta, agents, first, m, c_off, ncols, rho, -lr, momentum, local_steps, theta_out, scale, do_div,
+                         partial, part_off, nb);
+    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt}, Ints<0, 1, 2>{alg});
+  };
+  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
+  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
+  if (resid_total) {
+    // FedAvg / FedProx: no ||alpha||^2 partials were written; the second total is 0
+    hipLaunchKernelGGL(resid_reduce_kernel, dim3(dual ? 2 : 1), dim3(kThreads), 0, s, partial, nb, resid_total);
+    if (!dual) (void)hipMemsetAsync(resid_total + 1, 0, sizeof(double), s);
+  }
+  return check_launch(nm);
 }
 
 }  // namespace
@@ -636,43 +783,21 @@ int64_t dol_admm_ls_round_workspace_bytes(int32_t m, int64_t P) {
   return 2 * dol_admm_dual_workspace_bytes(m, P);  // ||w - theta||^2 and ||alpha||^2 partials
 }
 
+int dol_fed_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                         const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                         const int32_t* first, int32_t m, int64_t P, int32_t algorithm, float rho, float lr,
+                         float momentum, int32_t local_steps, double* resid_sq, double* alpha_sq, void* work,
+                         hipStream_t s) {
+  return fed_ls_round("dol_fed_ls_round_f32", w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents, first, m, P,
+                      algorithm, rho, lr, momentum, local_steps, resid_sq, alpha_sq, work, s);
+}
+
 int dol_admm_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
                           const float* target, int64_t ldt, const float* theta, const int32_t* agents,
                           const int32_t* first, int32_t m, int64_t P, float rho, float lr, float momentum,
                           int32_t local_steps, double* resid_sq, double* alpha_sq, void* work, hipStream_t s) {
-  DOL_DIMS_OK("dol_admm_ls_round_f32", ldw, ldb, lda, ldt, P);
-  const char* nm = "dol_admm_ls_round_f32";
-  const bool mom = momentum != 0.0f;
-  DOL_CHECKED(check_rows(nm, m < 0 || P < 0 || local_steps < 0, m == 0,
-                         P > 0 && (!w || !alpha || !target || !theta || (mom && !buf)), false, false));
-  if ((resid_sq == nullptr) != (alpha_sq == nullptr)) return fail(DOL_EINVAL, "%s: pass both residual outputs or neither", nm);
-  if (resid_sq && !work && P > 0) return fail(DOL_EINVAL, "%s: residuals need a workspace", nm);
-  if (ldw < P || lda < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
-  if (P == 0) {
-    if (resid_sq) {
-      (void)hipMemsetAsync(resid_sq, 0, sizeof(double) * m, s);
-      (void)hipMemsetAsync(alpha_sq, 0, sizeof(double) * m, s);
-    }
-    return check_launch(nm);
-  }
-  const bool vec = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
-                   (!mom || row_vec_ok(buf, ldb));
-  const int64_t per_block = int64_t(kThreads) * kDualIters;
-  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
-  if (mul_sat(chunks, m) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large", nm);
-  double* partial = static_cast<double*>(work);
-  const dim3 grid(static_cast<unsigned>(chunks * m));
-  dispatch([&](auto vc, auto mc, auto rc) {
-    hipLaunchKernelGGL((admm_ls_round_kernel<decltype(vc)::value, decltype(mc)::value, decltype(rc)::value>), grid,
-                       dim3(kThreads), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents, first, P, rho,
-                       -lr, momentum, local_steps, chunks, partial);
-  }, Bool{vec}, Bool{mom}, Bool{resid_sq != nullptr});
-  if (resid_sq) {
-    hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial, chunks, resid_sq);
-    hipLaunchKernelGGL(resid_reduce_kernel, dim3(m), dim3(kThreads), 0, s, partial + int64_t(m) * chunks, chunks,
-                       alpha_sq);
-  }
-  return check_launch(nm);
+  return fed_ls_round("dol_admm_ls_round_f32", w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents, first, m, P,
+                      DOL_FED_ADMM, rho, lr, momentum, local_steps, resid_sq, alpha_sq, work, s);
 }
 
 int64_t dol_admm_ls_round_mean_workspace_bytes(int64_t P) {
@@ -680,59 +805,24 @@ int64_t dol_admm_ls_round_mean_workspace_bytes(int64_t P) {
   return 2 * (cdiv(P, 64) + 2) * int64_t(sizeof(double));  // [2][blocks]: (w - theta)^2, alpha^2 (64-lane blocks)
 }
 
+int dol_fed_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                              const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                              const int32_t* first, int32_t m, int64_t P, int32_t algorithm, float rho, float lr,
+                              float momentum, int32_t local_steps, float* theta_out, float scale,
+                              double* resid_total, void* work, hipStream_t s) {
+  return fed_ls_round_mean("dol_fed_ls_round_mean_f32", w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents,
+                           first, m, P, algorithm, rho, lr, momentum, local_steps, theta_out, scale, resid_total,
+                           work, s);
+}
+
 int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
                                const float* target, int64_t ldt, const float* theta, const int32_t* agents,
                                const int32_t* first, int32_t m, int64_t P, float rho, float lr, float momentum,
                                int32_t local_steps, float* theta_out, float scale, double* resid_total, void* work,
                                hipStream_t s) {
-  DOL_DIMS_OK("dol_admm_ls_round_mean_f32", ldw, ldb, lda, ldt, P);
-  const char* nm = "dol_admm_ls_round_mean_f32";
-  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the average indexes w[0])", nm);
-  if (P < 0 || local_steps < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
-  if (!(scale > 0.0f)) return fail(DOL_EINVAL, "%s: scale must be > 0", nm);
-  const bool mom = momentum != 0.0f;
-  if (P > 0 && (!w || !alpha || !target || !theta || !theta_out || (mom && !buf)))
-    return fail(DOL_EINVAL, "%s: null pointer", nm);
-  if (theta_out == w || theta_out == alpha || theta_out == target || (mom && theta_out == buf))
-    return fail(DOL_EINVAL, "%s: theta_out aliases the rows", nm);
-  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
-  if (ldw < P || lda < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
-  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
-  if (P == 0) {
-    if (resid_total) (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
-    return check_launch(nm);
-  }
-  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) &&
-                      row_vec_ok(theta, 0) && row_vec_ok(theta_out, 0) && (!mom || row_vec_ok(buf, ldb));
-  const ColSplit cs = split_cols(P, vec_ok);
-  // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
-  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
-  // lanes per CU) take 256-lane strips: the strips are the only parallelism
-  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
-  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
-  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
-  // for the two-kernel round (row-major client round + ordered sum), which
-  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
-  const int n_cu = n_cus() > 0 ? n_cus() : 256;
-  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
-  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
-  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
-  const int64_t nb = nb4 + nbt;
-  double* partial = static_cast<double*>(work);
-  const int do_div = scale != 1.0f;
-  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
-    dispatch([&](auto mc, auto rc, auto ntc) {
-      hipLaunchKernelGGL((admm_ls_round_mean_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
-                                                    decltype(ntc)::value>),
-                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt,
-                         theta, agents, first, m, c_off, ncols, rho, -lr, momentum, local_steps, theta_out, scale, do_div,
-                         partial, part_off, nb);
-    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt});
-  };
-  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
-  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
-  if (resid_total) hipLaunchKernelGGL(resid_reduce_kernel, dim3(2), dim3(kThreads), 0, s, partial, nb, resid_total);
-  return check_launch(nm);
+  return fed_ls_round_mean("dol_admm_ls_round_mean_f32", w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents,
+                           first, m, P, DOL_FED_ADMM, rho, lr, momentum, local_steps, theta_out, scale, resid_total,
+                           work, s);
 }
 
 int dol_ordered_sum_f32(const float* W, int64_t ldw, const int32_t* order, int32_t m, int64_t P,

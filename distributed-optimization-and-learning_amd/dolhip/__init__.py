@@ -7,6 +7,8 @@ Layers:
   graph     communication_graph / Neighbors-as-CSR / ring plan (host)
   bank      AgentBank: stacked [N, ld] agent state in HBM, module views
   parallel  agent sharding over ranks: ring halo exchange, global mean
+  synthetic the separable workloads: SeparableDGD, and the server round of
+            SeparableADMM / SeparableFedAvg / SeparableFedProx (ops.fed_ls_round*)
 The reference-shaped APIs live beside this package:
   weighted_average/  (Simulator, DecFedAvg, FedLCon, Client, ...)
   primal_dual/       (Server, FedAvg_/FedProx_/FedAdmm_Server/_Client)

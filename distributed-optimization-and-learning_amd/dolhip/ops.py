@@ -31,6 +31,7 @@ __all__ = [
     "SLAB_CHUNK", "SLAB_ROWS", "csr_slab_pack", "mix_csr_slab", "slab_layout_ok", "dense_to_csr",
     "admm_ls_round_mean", "slab_variant", "SLAB_VARIANTS", "SPLIT3_FUSE_MAX_M", "SPLIT3_W_READY",
     "SPLIT3_X_ROWS_PADDED", "SPLIT3_FUSE_X", "AUTOTUNE_MIN_BYTES", "AUTOTUNE_REPS", "PM_MAX_FUSED_STEPS",
+    "FED_ALGORITHMS",
 ]
 
 PM_MAX_AGENTS = 8192  # dol_mix_csr_pm_f32: one p-row image (<= 32 KiB) per LDS stage
@@ -46,6 +47,7 @@ SLAB_VARIANTS = (2, 3)  # 2: the wave's pairs as one pipelined stream (r06); 3: 
 SPLIT3_W_READY, SPLIT3_X_ROWS_PADDED, SPLIT3_FUSE_X = 1, 2, 4  # dol_hip.h flags
 SPLIT3_FUSE_MAX_M = 2048  # auto-fused X split up to this many output rows (agents)
 OBJECTIVES = {"least_squares": 0, "logistic": 1}
+FED_ALGORITHMS = {"fedavg": 0, "fedprox": 1, "fedadmm": 2}  # DOL_FED_AVG / _PROX / _ADMM
 
 _TUNED: dict = {}  # launch choices tuned on the product path (see _auto_choice)
 _WORK: dict = {}  # per-device scratch (see _workspace)
@@ -843,13 +845,14 @@ def admm_ls_round_workspace_bytes(m: int, P: int) -> int:
     return int(_native.lib().dol_admm_ls_round_workspace_bytes(int(m), int(P)))
 
 
-def _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P):
-    """(P, n, ldw, lda, ldt, ldb) of a FedADMM least-squares round: the state
-    matrices of w's n rows, theta, the step count and the sampled `agents`."""
+def _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P, duals: bool = True):
+    """(P, n, ldw, lda, ldt, ldb) of a least-squares client round: the state
+    matrices of w's n rows, theta, the step count and the sampled `agents`.
+    duals=False (FedAvg / FedProx, fed_ls.py): alpha is not looked at, lda 0."""
     P = w.shape[1] if P is None else P
     n = w.shape[0]
     ldw = _check_rows("w", w, P)
-    lda = _check_rows("alpha", alpha, P, n, "alpha/target have fewer rows than w")
+    lda = _check_rows("alpha", alpha, P, n, "alpha/target have fewer rows than w") if duals else 0
     ldt = _check_rows("target", target, P, n, "alpha/target have fewer rows than w")
     _check_vec("theta", theta, P, w.device)
     if int(local_steps) < 0:
@@ -858,6 +861,30 @@ def _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, 
     if agents is not None:
         _check_order(agents, w.device)
     return P, n, ldw, lda, ldt, ldb
+
+
+def _check_distinct_agents(name: str, agents: Optional[torch.Tensor], n: int, validate: bool) -> int:
+    """m of a round + mean: the number of sampled `agents` (None: all n rows),
+    at least one and at most n.  validate: also that they are distinct rows
+    in [0, n), on the host (one device-to-host copy of the m ids) -- except
+    while the stream is being captured into a graph, where a copy to the host
+    cannot be made: capture with ids that the caller has checked."""
+    if agents is None:
+        m = n
+    else:
+        m = agents.numel()
+        if m > n:
+            raise ValueError(f"{name}: {m} agents but w has {n} rows (agents must be distinct)")
+        if validate and m:
+            with torch.cuda.device(agents.device):
+                capturing = torch.cuda.is_current_stream_capturing()
+            if not capturing:
+                ids = agents.cpu()
+                if int(ids.min()) < 0 or int(ids.max()) >= n or torch.unique(ids).numel() != m:
+                    raise ValueError(f"{name}: agents must be distinct rows in [0, {n})")
+    if m < 1:
+        raise ValueError(f"{name} needs at least one agent (the average indexes w[0])")
+    return m
 
 
 def admm_ls_round(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, theta: torch.Tensor,
@@ -908,20 +935,11 @@ def admm_ls_round_mean(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tenso
     rows before it stores the current ones, so a repeated id would read a
     stale row, and an out-of-range id would read and write out of bounds
     (ADVICE r05).  Callers that drew the ids themselves on the host and
-    checked them (SeparableADMM.round) pass validate=False.
+    checked them (SeparableADMM.round) pass validate=False.  The check is not
+    made while the stream is being captured into a graph.
     Reference: DEC/servers.py:50-81 (Server.run's round) on least squares."""
     P, n, ldw, lda, ldt, ldb = _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P)
-    m = n
-    if agents is not None:
-        m = agents.numel()
-        if m > n:
-            raise ValueError(f"admm_ls_round_mean: {m} agents but w has {n} rows (agents must be distinct)")
-        if validate and m:
-            ids = agents.cpu()
-            if int(ids.min()) < 0 or int(ids.max()) >= n or torch.unique(ids).numel() != m:
-                raise ValueError(f"admm_ls_round_mean: agents must be distinct rows in [0, {n})")
-    if m < 1:
-        raise ValueError("admm_ls_round_mean needs at least one agent (the average indexes w[0])")
+    m = _check_distinct_agents("admm_ls_round_mean", agents, n, validate)
     if first is not None:
         _check_array("first", first, torch.int32, m, w.device)
     if out is None:
@@ -1012,6 +1030,12 @@ def mlp_step(w: torch.Tensor, X: torch.Tensor, y: torch.Tensor, d: int, h: int, 
                  int(bool(first_step)), int(bool(update)), work.data_ptr(), _stream(w))
     return loss
 
+
+# ---------------------------------------------------------------------------
+# The least-squares round of FedAvg / FedProx / FedADMM (fed_ls.py, which
+# builds on the validators above): fed_ls_round, fed_ls_round_mean.
+# ---------------------------------------------------------------------------
+from .fed_ls import fed_ls_round, fed_ls_round_mean  # noqa: E402,F401
 
 # ---------------------------------------------------------------------------
 # Multi-step consensus on the parameter-major bank (pm_steps.py, which builds

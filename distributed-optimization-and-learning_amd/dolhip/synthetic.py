@@ -121,12 +121,23 @@ class SeparableADMM:
         residual metrics are per-rank partials, summed across ranks when
         `history` is read (a collective: every rank reads it).
     `round_fn` / `ordered_sum` inject CPU checkers in tests.
+
+    algorithm = "fedavg" / "fedprox" (SeparableFedAvg / SeparableFedProx) runs
+    the same Server.run with the other two clients of the reference
+    (FedAvg_Client / FedProx_Client, DEC/clients.py:85-95 / :101-115; their
+    update_duals is the base class's no-op, :58-59) through
+    dol_fed_ls_round_f32 / dol_fed_ls_round_mean_f32.  They keep no duals:
+    `alpha` is None and never allocated, `round_fn` is called with alpha=None
+    and alpha_sq=None, and `history` keeps its keys with dual_sq 0.0.  Sharding,
+    both means and the fused / two-kernel choice work as for FedADMM.
     """
 
     def __init__(self, n_agents: int, P: int, rho: float = 0.1, lr: float = 0.1, momentum: float = 0.5,
                  local_steps: int = 1, frac: float = 1.0, seed: int = 2028, device=None, mean: str = "exact",
                  group=None, metrics: bool = True, round_fn=None, ordered_sum=None, fused: Optional[bool] = None,
-                 shard: str = "agents"):
+                 shard: str = "agents", algorithm: str = "fedadmm"):
+        import functools
+
         import numpy as np
         import torch.distributed as dist
 
@@ -136,6 +147,10 @@ class SeparableADMM:
             raise ValueError("mean must be 'exact' or 'fast'")
         if shard not in ("agents", "columns"):
             raise ValueError("shard must be 'agents' or 'columns'")
+        if algorithm not in ops.FED_ALGORITHMS:
+            raise ValueError(f"algorithm must be one of {sorted(ops.FED_ALGORITHMS)}")
+        self.algorithm = algorithm
+        self.duals = algorithm == "fedadmm"
         self.shard = shard
         self.N, self.P = int(n_agents), int(P)
         self.rho, self.lr, self.mu, self.local_steps = float(rho), float(lr), float(momentum), int(local_steps)
@@ -154,7 +169,12 @@ class SeparableADMM:
         self.Pl = self.c1 - self.c0
         self.n = self.hi - self.lo
         self.device = torch.device(device) if device is not None else torch.device("cuda")
-        self._round = round_fn if round_fn is not None else ops.admm_ls_round
+        if self.duals:
+            own_round, own_round_mean = ops.admm_ls_round, ops.admm_ls_round_mean
+        else:
+            own_round = functools.partial(ops.fed_ls_round, algorithm=algorithm)
+            own_round_mean = functools.partial(ops.fed_ls_round_mean, algorithm=algorithm)
+        self._round = round_fn if round_fn is not None else own_round
         self._osum = ordered_sum if ordered_sum is not None else ops.ordered_sum
         # the client round and the mean in one pass (dol_admm_ls_round_mean_f32)
         # wherever the mean is this rank's ordered sum of its own rows: one
@@ -173,13 +193,13 @@ class SeparableADMM:
             # ranks (profiles/r06c_admm_narrow_ab.jsonl); same bits either way
             n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
             self.fused = self.Pl >= 4 * 1024 * n_cu
-        self._round_mean = ops.admm_ls_round_mean
+        self._round_mean = own_round_mean
         self._parallel = parallel
         self.rs = np.random.RandomState(seed)  # the reference's np.random.choice stream (setup_seed)
         ld = row_stride(max(self.Pl, 1))
         dev = self.device
         self.w = torch.zeros(max(self.n, 1), ld, dtype=torch.float32, device=dev)
-        self.alpha = torch.zeros_like(self.w)
+        self.alpha = torch.zeros_like(self.w) if self.duals else None
         self.target = torch.empty_like(self.w)
         self.mom = torch.zeros_like(self.w) if self.mu != 0.0 else None
         # per-row seeds over the whole row: identical rows (and column blocks) for every sharding
@@ -228,7 +248,7 @@ class SeparableADMM:
                 first = torch.as_tensor(~self.mom_started[local], dtype=torch.int32, device=dev)
             if self.metrics:
                 rw = torch.empty(ml, dtype=torch.float64, device=dev)
-                ra = torch.empty(ml, dtype=torch.float64, device=dev)
+                ra = torch.empty(ml, dtype=torch.float64, device=dev) if self.duals else None
             self._round(self.w, self.alpha, self.target, self.theta, agents=rows, first=first, buf=self.mom,
                         rho=self.rho, lr=self.lr, momentum=self.mu, local_steps=self.local_steps, resid_sq=rw,
                         alpha_sq=ra, P=self.P)
@@ -246,7 +266,8 @@ class SeparableADMM:
             s = torch.zeros(2, dtype=torch.float64, device=dev)
             if ml:
                 s[0] = rw.sum()
-                s[1] = ra.sum()
+                if ra is not None:
+                    s[1] = ra.sum()
             if self.world > 1:
                 self._all_reduce(s)
             self._pending.append((self.rounds, s))
@@ -284,14 +305,15 @@ class SeparableADMM:
                 rw = ra = None
                 if self.metrics:
                     rw = torch.empty(m, dtype=torch.float64, device=dev)
-                    ra = torch.empty(m, dtype=torch.float64, device=dev)
+                    ra = torch.empty(m, dtype=torch.float64, device=dev) if self.duals else None
                 self._round(self.w, self.alpha, self.target, self.theta, agents=rows, first=first, buf=self.mom,
                             rho=self.rho, lr=self.lr, momentum=self.mu, local_steps=self.local_steps, resid_sq=rw,
                             alpha_sq=ra, P=self.Pl)
                 self._osum(self.w, rows, out=self._theta_next, scale=float(m), P=self.Pl)
                 if self.metrics:
                     s[0] = rw.sum()
-                    s[1] = ra.sum()
+                    if ra is not None:
+                        s[1] = ra.sum()
         if self.mom is not None and self.local_steps > 0:
             self.mom_started[order] = True
         self.theta, self._theta_next = self._theta_next, self.theta
@@ -380,7 +402,13 @@ class SeparableADMM:
 
     def fixed_point(self) -> torch.Tensor:
         """theta* = (mean_k t_k + rho*theta_0) / (1 + rho): where the reference's
-        iteration settles under full participation (see the class docstring)."""
+        iteration settles under full participation (see the class docstring).
+        FedAvg / FedProx: optimum().  With every client sampled the round is
+        the same affine map of (theta, t_k, buf_k) for every client, so the
+        mean of the rows follows one client's iteration on mean_k t_k, and
+        theta = mean_k t_k with zero mean momentum is stationary."""
+        if not self.duals:
+            return self.optimum()
         theta0 = self.theta0[:self.P] if self.shard != "columns" or self.world == 1 else \
             self._gather_columns(self.theta0[:self.Pl])
         return (self.optimum() + self.rho * theta0.double()) / (1.0 + self.rho)
@@ -388,6 +416,24 @@ class SeparableADMM:
     def distance_to_fixed_point(self) -> float:
         """||theta - theta*|| / sqrt(P) (full participation)."""
         return float((self.full_theta().double() - self.fixed_point()).norm() / self.P ** 0.5)
+
+
+class SeparableFedAvg(SeparableADMM):
+    """SeparableADMM's round with the reference's FedAvg client: plain local
+    momentum SGD on the least-squares loss (DEC/clients.py:85-95), no duals.
+    rho is not used."""
+
+    def __init__(self, n_agents: int, P: int, **kw):
+        super().__init__(n_agents, P, algorithm="fedavg", **kw)
+
+
+class SeparableFedProx(SeparableADMM):
+    """SeparableADMM's round with the reference's FedProx client: the proximal
+    term rho * (w - theta) on every local gradient (DEC/clients.py:101-115), no
+    duals."""
+
+    def __init__(self, n_agents: int, P: int, **kw):
+        super().__init__(n_agents, P, algorithm="fedprox", **kw)
 
 
 class SeparableDGDPM:

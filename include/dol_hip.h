@@ -459,6 +459,63 @@ int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, f
 int64_t dol_admm_ls_round_mean_workspace_bytes(int64_t P);
 
 /*
+ * The least-squares client round of all three algorithms that the reference's
+ * one Server.run drives (DEC/servers.py:50-81): dol_admm_ls_round_f32 with the
+ * gradient term chosen by `algorithm`.  Replaces Client.update_weights
+ * (DEC/clients.py:36-53) with the CNN gradient swapped for the exact
+ * least-squares one, for agent row a = agents[k] (agents NULL: a = k):
+ *   w = theta                                                    (:37)
+ *   local_steps times:  g = fl(w - t_a)
+ *     DOL_FED_AVG   g' = g                                       (FedAvg_Client.update_model, :85-95)
+ *     DOL_FED_PROX  g' = fl(g + fl(rho * fl(w - theta)))         (FedProx_Client.update_model, :101-115)
+ *     DOL_FED_ADMM  g' = fl(g + fl(alpha + fl(rho * fl(w - theta))))   (FedAdmm_Client.update_model, :125-139)
+ *     momentum != 0: buf = (first[k] && step 0) ? g' : fl(fl(buf*momentum) + g'); d = buf
+ *     momentum == 0: d = g'
+ *     w = fma(-lr, d, w)                                         (SGD.step, :44)
+ *   DOL_FED_ADMM only: alpha = fl(alpha + fl(rho * fl(w - theta)))     (update_duals, :141-144;
+ *                      the base class's is a no-op, :58-59)
+ * FedAvg is not FedADMM with rho = 0 and zero duals: adding fl(0 + fl(0 * x))
+ * turns a gradient of -0 into +0, and the rows differ in the sign of zero.
+ * algorithm == DOL_FED_ADMM is dol_admm_ls_round_f32, bit for bit.  For the
+ * other two alpha and alpha_sq must be NULL (DOL_EINVAL otherwise), lda is
+ * ignored, and no dual row is read or written: per sampled agent the round
+ * streams t (, buf) in and w (, buf) out.  rho is ignored by DOL_FED_AVG.
+ * resid_sq alone is allowed there: ||w_k - theta||^2, the client drift, fp64
+ * [m] in a fixed order; with DOL_FED_ADMM resid_sq and alpha_sq come both or
+ * neither.  algorithm outside 0..2: DOL_EINVAL.  Workspace:
+ * dol_admm_ls_round_workspace_bytes(m, P).  Nothing allocates or synchronises.
+ */
+#define DOL_FED_AVG 0
+#define DOL_FED_PROX 1
+#define DOL_FED_ADMM 2
+int dol_fed_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                         const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                         const int32_t* first, int32_t m, int64_t P, int32_t algorithm, float rho, float lr,
+                         float momentum, int32_t local_steps, double* resid_sq, double* alpha_sq, void* work,
+                         hipStream_t s);
+
+/*
+ * dol_fed_ls_round_f32 fused with the server's ordered average
+ * (average_weights, DEC/servers.py:42-48): the whole round of
+ * DEC/servers.py:50-81 in one pass, for any of the three algorithms.
+ * algorithm == DOL_FED_ADMM is dol_admm_ls_round_mean_f32, bit for bit; the
+ * rows of the other two come out as dol_fed_ls_round_f32 leaves them, and
+ * theta_out = fl(acc / scale) (scale != 1) of acc = w[agents[0]]; acc =
+ * fl(acc + w[agents[k]]) on the new rows.  alpha must be NULL for
+ * DOL_FED_AVG / DOL_FED_PROX (lda ignored).  resid_total (nullable, fp64 [2]):
+ * [0] the round's sum over the agents of ||w_k - theta||^2, [1] that of
+ * ||alpha_k||^2, written 0 for FedAvg / FedProx.  Every other rule is
+ * dol_admm_ls_round_mean_f32's: agents DISTINCT, m >= 1, P < 2^29, theta_out
+ * may alias theta and must not alias the rows, workspace
+ * dol_admm_ls_round_mean_workspace_bytes(P).  Nothing allocates or synchronises.
+ */
+int dol_fed_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
+                              const float* target, int64_t ldt, const float* theta, const int32_t* agents,
+                              const int32_t* first, int32_t m, int64_t P, int32_t algorithm, float rho, float lr,
+                              float momentum, int32_t local_steps, float* theta_out, float scale,
+                              double* resid_total, void* work, hipStream_t s);
+
+/*
  * Ordered uniform average, replacing Server.average_weights
  *   DEC/servers.py:42-48:  acc = w[order[0]]; acc = fl(acc + w[order[k]]) k=1..m-1;
  *                          theta = fl(acc / (float)m)
