@@ -183,15 +183,22 @@ __device__ __forceinline__ void stv(V* p, V v) {
 //   x = fma(-lr, d, x)
 // load() is issued with the mixing loads; apply() runs after the mix.
 // ----------------------------------------------------------------------------
+// The gradient of the separable loss on one coordinate, written once: the local
+// steps below, the gradient-tracking round (csr_pm_gt_kernel) and
+// dol_separable_grad_f32 all call it.
+template <int OBJ>
+__device__ __forceinline__ float separable_grad(float x, float t) {
+  if constexpr (OBJ == 0) return x - t;
+  else return -t / (1.0f + expf(t * x));
+}
+
 // The local steps on one coordinate: the one place this arithmetic is written
 // (DgdEpi on the agent-major bank, csr_pm_kernel on the parameter-major one).
 // e: the epilogue's arguments, read where they are used (e.steps, e.mom, e.neg_lr).
 template <int OBJ, int MODE, class E>
 __device__ __forceinline__ float dgd_local_steps(float x, float t, float& b, const E& e) {
   for (int s = 0; s < e.steps; ++s) {
-    float g;
-    if constexpr (OBJ == 0) g = x - t;
-    else g = -t / (1.0f + expf(t * x));
+    const float g = separable_grad<OBJ>(x, t);
     float d = g;
     if constexpr (MODE != 0) {
       if (MODE == 1 && s == 0) b = g;

@@ -50,6 +50,33 @@
 // fused round, eps 5, 1024 x 2^20: least squares + momentum 6.73 ms against
 // 10.00 for four mixes and the round, logistic 6.73 against 8.74.
 //
+// csr_pm_gt_kernel: config 3's gradient-tracking round (x' = W x - lr s,
+// s' = W s + g(x') - g(x)) in the same pipeline.  A stage holds X, S and T
+// images; X and S are gathered through the same Quad, the own x, s, t are f4
+// LDS reads, g is recomputed: 5 N P 4 bytes per round.  91 (least squares) /
+// 89 (logistic) VGPRs, no scratch (hipcc's resource remarks); built on
+// issue_stage it took 128 VGPRs and 20-28 B of scratch at 80 KiB stages, hence
+// its own packed stage issue.  Geometry, rr4 + Metropolis self weights, least
+// squares / logistic ms at 1024 x 2^20 (4096 x 2^18), profiles/gt_pm_geom.jsonl:
+//   80 KiB x 2  3.88 / 4.71 (3.67 / 4.65)     <- least squares
+//   64 KiB x 2  4.17 / 4.47 (4.17 / 4.46)
+//   48 KiB x 3  4.23 / 4.42 (4.23 / 4.43)     <- logistic
+// Legs (tools/gt_pm_ab.py, profiles/gt_pm_ab.jsonl; one process, same buffers,
+// medians of 5 windows): (a) the round composed from two mixes, two gradient
+// passes and the elementwise ops, (b) this kernel, (c) the least-squares +
+// momentum DGD round above (the same five streams); HBM = 5 N P 4 bytes over
+// (b) at 8 TB/s:
+//   1024 x 2^20  least squares (a) 20.46 (b) 4.13 (c) 3.82 ms, (b)/(a) 0.20, (b)/(c) 1.08, HBM 65 %
+//                logistic      (a) 20.42 (b) 4.22 (c) 3.82,    0.21, 1.11, 64 %
+//   4096 x 2^18  least squares (a) 20.52 (b) 3.53 (c) 3.83,    0.17, 0.92, 76 %
+//                logistic      (a) 20.49 (b) 4.24 (c) 3.83,    0.21, 1.11, 63 %
+// (b) moved between 3.64 and 3.98 ms from process to process.  The S gather
+// replaced by the own-element read (a build for that measurement only,
+// profiles/gt_pm_probe.jsonl): least squares 3.92-3.98 ms, no gain; logistic
+// 3.99-4.03 against 4.24-4.27.  Counters per launch at 1024 x 2^20
+// (profiles/gt_pm_counters.json): FETCH_SIZE 6 291 733 KiB (x 2: 1.00004 x the
+// 3 N P 4 read), WRITE_SIZE 8 389 153 KiB (1.00006 x the 2 N P 4 written).
+//
 // Tried and retired (each was a launch variant behind an environment switch;
 // the code last existed in commit 2d96633):
 //  * DOL_PM_DGD_GEOM, the fused round's stage geometry forced to 64 KiB x 2,
@@ -443,6 +470,218 @@ __global__ __launch_bounds__(T) void csr_pm_steps_kernel(const float* __restrict
 }
 
 // ----------------------------------------------------------------------------
+// The gradient-tracking round (DIGing / NEXT) of config 3 in one pass:
+//   x_i' = sum_j W_ij x_j - lr s_i
+//   s_i' = sum_j W_ij s_j + grad f_i(x_i') - grad f_i(x_i)
+// with W = W_off (CSR) + diag(self_w).  Not in the reference, which has no
+// decentralised optimiser beyond the consensus round (DIST/simulators.py:
+// 147-162); the mix is its consensus (DIST/clients.py:61-69).  Per coordinate:
+//   ax = mix_quad over the X image, as = mix_quad over the S image (same Quad)
+//   self weights:  ax = fl(ax + fl(d x)),  as = fl(as + fl(d s))
+//   x' = fma(-lr, s, ax);   s' = fl(fl(as + g(x', t)) - g(x, t))
+// g = separable_grad<OBJ> (dol_launch.h).  A stage holds sr p-rows of three
+// images -- X and S xw floats each (both are gathered), T nw floats -- that
+// come in by one LDS-DMA ring; the agent's own x, s, t are f4 LDS reads of the
+// same images, so no gradient matrix is stored or streamed: X, S, T in, X', S'
+// out, 5 x 4 bytes per coordinate.
+// ----------------------------------------------------------------------------
+struct PmGt {
+  const float* S; int64_t ld_s;
+  float* XO; int64_t ldxo;
+  float* SO; int64_t ldso;
+  const float* T; int64_t ldt;
+  const float* D;  // self weights [n_rows] or NULL
+  float neg_lr;
+};
+
+// four self weights of quad q from clamped addresses (as load_quad); zeros without D
+__device__ __forceinline__ f4 load_self_weights(const float* __restrict__ D, int q, int n_rows) {
+  if (!D) return f4{0.f, 0.f, 0.f, 0.f};
+  float d[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) d[a] = D[min(4 * q + a, n_rows - 1)];
+  return f4{d[0], d[1], d[2], d[3]};
+}
+
+template <int OBJ>
+__device__ __forceinline__ void gt_lane(float ax, float as, float x, float s, float t, float d, bool self,
+                                        float neg_lr, float& xo, float& so) {
+  if (self) {
+    ax = ax + d * x;
+    as = as + d * s;
+  }
+  xo = __builtin_fmaf(neg_lr, s, ax);
+  so = (as + separable_grad<OBJ>(xo, t)) - separable_grad<OBJ>(x, t);
+}
+
+// One stage of the round: the X images at im0, the S images behind them, the
+// T images behind those; two buffer stores per (p-row, quad), dead lanes
+// pointed out of range as in mix_stage.
+template <int T, int OBJ>
+__device__ __forceinline__ void gt_stage(const Quad (&Q)[1], f4 dw, const float* __restrict__ im0, const PmGt& e,
+                                         int n_rows, int64_t P, int64_t p0, int xw, int nw, int sr, int spt, int q0,
+                                         int g, int GR, const int32_t* __restrict__ rowptr,
+                                         const int32_t* __restrict__ col, const float* __restrict__ val) {
+  const int nq = (n_rows + 3) / 4;
+  const int64_t rows_here = std::min<int64_t>(sr, P - p0);
+  const rsrc_t rx = make_rsrc(e.XO + p0 * e.ldxo, static_cast<uint32_t>(rows_here * e.ldxo * 4));
+  const rsrc_t rs = make_rsrc(e.SO + p0 * e.ldso, static_cast<uint32_t>(rows_here * e.ldso * 4));
+  const float* sim0 = im0 + sr * xw;
+  const float* tim0 = sim0 + sr * xw;
+  const bool self = e.D != nullptr;
+  const int q = q0;
+  const int qc = q < nq ? q : 0;
+  for (int u = 0; u < spt; ++u) {
+    const int pr = g + u * GR;
+    const bool prow_ok = pr < rows_here;
+    const int prc = pr < sr ? pr : 0;
+    const float* xim = im0 + prc * xw;
+    const float* sim = sim0 + prc * xw;
+    const f4 ax = mix_quad(Q[0], xim, q, rowptr, col, val);
+    const f4 as = mix_quad(Q[0], sim, q, rowptr, col, val);
+    const f4 xv = *reinterpret_cast<const f4*>(xim + 4 * qc);
+    const f4 sv = *reinterpret_cast<const f4*>(sim + 4 * qc);
+    const f4 tv = *reinterpret_cast<const f4*>(tim0 + prc * nw + 4 * qc);
+    float xe[4], se[4];
+    gt_lane<OBJ>(ax.x, as.x, xv.x, sv.x, tv.x, dw.x, self, e.neg_lr, xe[0], se[0]);
+    gt_lane<OBJ>(ax.y, as.y, xv.y, sv.y, tv.y, dw.y, self, e.neg_lr, xe[1], se[1]);
+    gt_lane<OBJ>(ax.z, as.z, xv.z, sv.z, tv.z, dw.z, self, e.neg_lr, xe[2], se[2]);
+    gt_lane<OBJ>(ax.w, as.w, xv.w, sv.w, tv.w, dw.w, self, e.neg_lr, xe[3], se[3]);
+    const f4 xo{xe[0], xe[1], xe[2], xe[3]}, so{se[0], se[1], se[2], se[3]};
+    const uint32_t offx = static_cast<uint32_t>((pr * e.ldxo + 4 * q) * 4);
+    const uint32_t offs = static_cast<uint32_t>((pr * e.ldso + 4 * q) * 4);
+    if (4 * q + 3 < n_rows || q >= nq) {  // whole quad, or none (dropped)
+      const bool ok = prow_ok && q < nq;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, xo), rx, ok ? offx : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, so), rs, ok ? offs : kOOB, 0, kNT);
+    } else {  // the ragged last quad (elements named one by one: hipcc 7.2 stored
+              // element 0 four times from a loop over y[a] here)
+      const int left = n_rows - 4 * q;  // 1..3
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[0]), rx, prow_ok ? offx : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[1]), rx, prow_ok && left > 1 ? offx + 4 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[2]), rx, prow_ok && left > 2 ? offx + 8 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[0]), rs, prow_ok ? offs : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[1]), rs, prow_ok && left > 1 ? offs + 4 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[2]), rs, prow_ok && left > 2 ? offs + 8 : kOOB, 0,
+                                            kNT);
+    }
+  }
+}
+
+// T threads per workgroup, SF floats per stage buffer, NBUF buffers; one quad
+// per thread (at most 4 T agents).  The ring, the counted wait and the stage
+// order are csr_pm_kernel's; kStores = 2.
+template <int T, int SF, int NBUF, int OBJ>
+__global__ __launch_bounds__(T) void csr_pm_gt_kernel(const float* __restrict__ XT, int64_t ldx, int n_rows,
+                                                      int64_t P, int xw, int sr, int qp_log2, int spt,
+                                                      int64_t n_stages, int nseg,
+                                                      const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col,
+                                                      const float* __restrict__ val, PmGt e, int nw) {
+  constexpr int kDma = SF / 4 / T;
+  static_assert(kDma * 4 * T == SF, "a stage is a whole number of DMA rounds");
+  extern __shared__ __attribute__((aligned(16))) float img[];  // NBUF x SF
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = tid & ((1 << qp_log2) - 1);
+  const int g = tid >> qp_log2;
+  const int GR = T >> qp_log2;
+  const int nnz = rowptr[n_rows];
+  Quad Q[1];
+  if (nnz > 0) load_quad(Q[0], q0, n_rows, nnz, rowptr, col, val);
+  else Q[0] = Quad{};
+  const f4 dw = load_self_weights(e.D, q0, n_rows);
+
+  const int64_t W = gridDim.x / nseg, seg = blockIdx.x % nseg, wl = blockIdx.x / nseg;
+  const int64_t seg_len = (n_stages + nseg - 1) / nseg;
+  const int64_t seg_n = std::max<int64_t>(0, std::min<int64_t>(seg_len, n_stages - seg * seg_len));
+  const int64_t nk = wl < seg_n ? (seg_n - wl + W - 1) / W : 0;
+  auto stage_of = [&](int64_t k) { return seg * seg_len + wl + k * W; };
+  // This thread's kDma pieces of a stage, classified once: piece d is 16 B of
+  // operand sel (0 X, 1 S, 2 T; 3 dead) in p-row pr of the stage, poff floats
+  // from that operand's row p0 (pmeta = pr | sel << 16).  issue_stage keeps
+  // about 11 registers per piece live across the stage loop; with three
+  // operands and five pieces the kernel then spilled, hence the packing.
+  const int xq = xw / 4, nq4 = nw / 4, nr4 = (n_rows + 3) / 4;
+  const int nX = sr * xq, nTM = sr * nq4;
+  int poff[kDma], pmeta[kDma];
+#pragma unroll
+  for (int d = 0; d < kDma; ++d) {
+    const int pc = d * T + tid;
+    int sel = 3, pr = 0, off = 0;
+    if (pc < 2 * nX) {
+      const int h = pc >= nX ? 1 : 0, ps = pc - h * nX;
+      pr = ps / xq;
+      const int j4 = ps - pr * xq;
+      if (j4 < nr4) {
+        sel = h;
+        off = static_cast<int>(pr * (h ? e.ld_s : ldx)) + 4 * j4;
+      }
+    } else if (pc - 2 * nX < nTM) {
+      const int pt = pc - 2 * nX;
+      pr = pt / nq4;
+      sel = 2;
+      off = static_cast<int>(pr * e.ldt) + 4 * (pt - pr * nq4);
+    }
+    poff[d] = off;
+    pmeta[d] = pr | sel << 16;
+  }
+  auto issue = [&](int64_t k) {  // stage k of this workgroup -> buffer k % NBUF; dead pieces re-read XT[0..3]
+    float* dst = img + (k % NBUF) * SF;
+    const int64_t p0 = stage_of(k) * sr;
+    const float* bx = XT + p0 * ldx;
+    const float* bs = e.S + p0 * e.ld_s;
+    const float* bt = e.T + p0 * e.ldt;
+#pragma unroll
+    for (int d = 0; d < kDma; ++d) {
+      const int sel = pmeta[d] >> 16, pr = pmeta[d] & 0xffff;
+      const float* base = sel == 0 ? bx : sel == 1 ? bs : bt;
+      const float* src = sel != 3 && p0 + pr < P ? base + poff[d] : XT;
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, kNT);
+    }
+  };
+  constexpr int kStores = 2;  // buffer stores per (p-row, quad): X' and S'
+#pragma unroll
+  for (int k = 0; k < NBUF - 1; ++k)
+    if (k < nk) issue(k);
+  for (int64_t k = 0; k < nk; ++k) {
+    const int64_t ahead = std::min<int64_t>(nk - 1, k + NBUF - 2) - k;
+    wait_vmcnt(static_cast<int>(std::min<int64_t>(63, kStores * spt * std::min<int64_t>(k, NBUF - 1) + kDma * ahead)));
+    __builtin_amdgcn_s_barrier();  // every wave's share landed; buffer (k-1) % NBUF is free
+    if (k + NBUF - 1 < nk) issue(k + NBUF - 1);
+    gt_stage<T, OBJ>(Q, dw, img + (k % NBUF) * SF, e, n_rows, P, stage_of(k) * sr, xw, nw, sr, spt, q0, g, GR, rowptr,
+                     col, val);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this stage's LDS reads are done before the next barrier
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// G = g(X, T) elementwise over rows x cols (V = f4 columns or the scalar tail
+// from c_off), row loads and stores nontemporal; either bank layout.
+template <typename V, int OBJ>
+__global__ __launch_bounds__(256) void separable_grad_kernel(const float* X, int64_t ldx, const float* Tg, int64_t ldt,
+                                                             float* G, int64_t ldg, int64_t c_off,
+                                                             int64_t ncols_v, int64_t n_col_tiles) {
+  const int64_t blk = blockIdx.x;
+  const int64_t r = blk / n_col_tiles;
+  const int64_t c = (blk % n_col_tiles) * 256 + threadIdx.x;
+  if (c >= ncols_v) return;
+  const V x = ldv<V, true>(reinterpret_cast<const V*>(X + r * ldx + c_off) + c);
+  const V t = ldv<V, true>(reinterpret_cast<const V*>(Tg + r * ldt + c_off) + c);
+  V gv;
+  if constexpr (Vec<V>::W == 1) {
+    gv = separable_grad<OBJ>(x, t);
+  } else {
+    gv = V{separable_grad<OBJ>(x.x, t.x), separable_grad<OBJ>(x.y, t.y), separable_grad<OBJ>(x.z, t.z),
+           separable_grad<OBJ>(x.w, t.w)};
+  }
+  stv<V, true>(reinterpret_cast<V*>(G + r * ldg + c_off) + c, gv);
+}
+
+// ----------------------------------------------------------------------------
 // Tiled transpose B[c][r] = A[r][c] (fp32, 64 x 64 tiles through LDS, rows
 // padded by one float against bank conflicts): converts the agent-major bank
 // to the parameter-major one and back (setup / checkpoint time, not per round).
@@ -601,9 +840,109 @@ int mix_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, int32_t x_rows
   return check_launch(nm);
 }
 
+constexpr int kGtMaxAgents = 4 * kT1;  // one quad per thread
+
+// The gradient-tracking round: validation in mix_csr_pm_impl's order, then
+// csr_pm_gt_kernel in the small geometry (1024-thread workgroups, one per CU,
+// one quad per thread).
+int gt_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, const float* ST, int64_t ld_s, float* XO,
+                   int64_t ldxo, float* SO, int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr,
+                   const int32_t* col, const float* val, const float* self_w, const float* TT, int64_t ldt,
+                   int32_t objective, float lr, int32_t nseg_req, hipStream_t s) {
+  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
+  if (nseg_req < 0 || nseg_req > 256) return fail(DOL_EINVAL, "%s: stage order %d outside [0, 256]", nm, nseg_req);
+  if (n < 0 || P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (n == 0 || P == 0) { dol::g_err[0] = '\0'; return DOL_OK; }
+  if (!XT || !ST || !XO || !SO || !TT || !rowptr || !col || !val) return fail(DOL_EINVAL, "%s: null pointer", nm);
+  if (n > kGtMaxAgents)
+    return fail(DOL_EINVAL, "%s: the gradient-tracking round takes at most %d agents (got %d)", nm, kGtMaxAgents, n);
+  const int nq = (n + 3) / 4;
+  const int nw = 4 * nq;
+  for (const int64_t ld : {ldx, ld_s, ldxo, ldso, ldt})
+    if (ld % 4 || ld < nw)
+      return fail(DOL_EINVAL, "%s: leading dimensions must be multiples of 4 covering the rounded-up agent count", nm);
+  if ((reinterpret_cast<uintptr_t>(XT) | reinterpret_cast<uintptr_t>(ST) | reinterpret_cast<uintptr_t>(XO) |
+       reinterpret_cast<uintptr_t>(SO) | reinterpret_cast<uintptr_t>(TT)) & 15u)
+    return fail(DOL_EINVAL, "%s: XT, ST, XO, SO and TT must be 16-B aligned", nm);
+  if (XT == ST || XT == XO || XT == SO || ST == XO || ST == SO || XO == SO)
+    return fail(DOL_EINVAL, "%s: XT, ST, XO and SO alias (a Jacobi update of both needs four buffers)", nm);
+  // geometry: X + S + T p-rows per stage, 2 xw + nw floats each (48 KiB at
+  // 4096 agents, so every agent count fits either ring): 80 KiB x 2 for least
+  // squares, 48 KiB x 3 for logistic, the rings that won (the file's header)
+  const int xw = (n + 255) / 256 * 256;
+  const int SF = objective == 0 ? 20480 : 12288;
+  const int NB = objective == 0 ? 2 : 3;  // must match the kernel's NBUF (LDS size)
+  int sr = SF / (2 * xw + nw);
+  int qp_log2 = 0;
+  while ((1 << qp_log2) < nq) ++qp_log2;
+  const int gr = kT1 >> qp_log2;
+  if (sr >= gr) sr = std::min(sr / gr * gr, 4 * gr);
+  const int spt = (sr + gr - 1) / gr;
+  if (sr < 1) return fail(DOL_EINVAL, "%s: a p-row of X, S and T exceeds a stage", nm);
+  // a stage's offsets are 32-bit: the stores' buffer offsets and the DMA pieces' float offsets
+  if (int64_t(sr) * std::max({ldx, ld_s, ldxo, ldso, ldt}) * 4 >= (int64_t(1) << 31))
+    return fail(DOL_EINVAL, "%s: leading dimension too large", nm);
+  const int64_t n_stages = (P + sr - 1) / sr;
+  const int ncu = n_cus();
+  if (ncu <= 0) return fail(DOL_EINVAL, "%s: no device", nm);
+  const int64_t grid = std::min<int64_t>(ncu, n_stages);
+  const int proc = g_pm_nseg.load(std::memory_order_relaxed);
+  int nseg = nseg_req > 0 ? nseg_req : proc > 0 ? proc : env_int("DOL_PM_NSEG", 8);
+  if (nseg < 1 || grid % nseg) nseg = 1;
+  const PmGt e{ST, ld_s, XO, ldxo, SO, ldso, TT, ldt, self_w, -lr};
+  auto go = [&](auto kern) {
+    const int lds = NB * SF * 4;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kT1), lds, s, XT, ldx, n, P, xw, sr, qp_log2, spt,
+                       n_stages, nseg, rowptr, col, val, e, nw);
+  };
+  if (objective == 0) go(csr_pm_gt_kernel<kT1, 20480, 2, 0>);
+  else go(csr_pm_gt_kernel<kT1, 12288, 3, 1>);
+  return check_launch(nm);
+}
+
 }  // namespace
 
 extern "C" {
+
+int dol_gt_csr_pm_f32(const float* XT, int64_t ldx, const float* ST, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                      int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                      const float* val, const float* self_w, const float* TT, int64_t ldt, int32_t objective,
+                      float lr, hipStream_t s) {
+  return dol_gt_csr_pm_ex_f32(XT, ldx, ST, lds, XO, ldxo, SO, ldso, n, P, rowptr, col, val, self_w, TT, ldt, objective,
+                              lr, 0, s);
+}
+
+int dol_gt_csr_pm_ex_f32(const float* XT, int64_t ldx, const float* ST, int64_t lds, float* XO, int64_t ldxo,
+                         float* SO, int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                         const float* val, const float* self_w, const float* TT, int64_t ldt, int32_t objective,
+                         float lr, int32_t nseg, hipStream_t s) {
+  DOL_DIMS_OK("dol_gt_csr_pm_f32", ldx, lds, ldxo, ldso, ldt, P);
+  return gt_csr_pm_impl("dol_gt_csr_pm_f32", XT, ldx, ST, lds, XO, ldxo, SO, ldso, n, P, rowptr, col, val, self_w, TT,
+                        ldt, objective, lr, nseg, s);
+}
+
+int dol_separable_grad_f32(const float* X, int64_t ldx, const float* T, int64_t ldt, float* G, int64_t ldg,
+                           int64_t rows, int64_t cols, int32_t objective, hipStream_t s) {
+  const char* nm = "dol_separable_grad_f32";
+  DOL_DIMS_OK(nm, ldx, ldt, ldg, rows, cols);
+  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
+  DOL_CHECKED(check_rows(nm, rows < 0 || cols < 0, rows == 0 || cols == 0, !X || !T || !G,
+                         ldx < cols || ldt < cols || ldg < cols, false, "", "ld < cols"));
+  const ColSplit cs = split_cols(cols, row_vec_ok(X, ldx) && row_vec_ok(T, ldt) && row_vec_ok(G, ldg));
+  if (mul_sat(cdiv(cs.n4 + cs.tail, 256), rows) > kMaxBlocks) return fail(DOL_EINVAL, "%s: too large", nm);
+  auto launch = [&](auto vtag, int64_t c_off, int64_t nc) {
+    using V = decltype(vtag);
+    const int64_t nct = cdiv(nc, 256);
+    dispatch([&](auto oc) {
+      hipLaunchKernelGGL((separable_grad_kernel<V, decltype(oc)::value>), dim3(static_cast<unsigned>(nct * rows)),
+                         dim3(256), 0, s, X, ldx, T, ldt, G, ldg, c_off, nc, nct);
+    }, Ints<0, 1>{objective});
+  };
+  if (cs.n4 > 0) launch(f4{}, 0, cs.n4);
+  if (cs.tail > 0) launch(float{}, cs.n4 * 4, cs.tail);
+  return check_launch(nm);
+}
 
 int dol_mix_csr_pm_f32(const float* XT, int64_t ldx, int32_t x_rows, float* YT, int64_t ldy, int32_t n_rows,
                        int64_t P, const int32_t* rowptr, const int32_t* col, const float* val, hipStream_t s) {

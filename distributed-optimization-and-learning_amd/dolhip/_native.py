@@ -85,6 +85,11 @@ SIGNATURES = {
                                  _i32, _i32, _f32, _f32, ctypes.c_int, _ptr],
     "dol_dgd_csr_pm_steps_ex_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i32,
                                     _i32, _i32, _f32, _f32, ctypes.c_int, _i32, _ptr],
+    "dol_gt_csr_pm_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                          _i64, _i32, _f32, _ptr],
+    "dol_gt_csr_pm_ex_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                             _i64, _i32, _f32, _i32, _ptr],
+    "dol_separable_grad_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i32, _ptr],
     "dol_transpose_f32": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr],
     "dol_csr_slab_nk": [_i32],
     "dol_csr_slab_hdr_len": [_i32, _i32],

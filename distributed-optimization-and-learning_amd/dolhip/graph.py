@@ -306,6 +306,40 @@ def random_regular_csr(n: int, degree: int = 4, seed: int = 2028) -> CSR:
     return CSR(n, n, rowptr.astype(np.int32), cols_w.astype(np.int32), vals_w)
 
 
+def metropolis_weights(csr: CSR):
+    """(W_off, d): Metropolis-Hastings weights on the sparsity pattern of
+    `csr`, as a zero-diagonal CSR and the self-weight vector d (float32 [n]),
+    so that W = W_off + diag(d) is symmetric and doubly stochastic with a
+    positive diagonal -- what gradient tracking needs (ops.gt_csr_pm takes d as
+    `self_weight`).  Only the pattern is used: values, diagonal entries and
+    duplicates are ignored; it must be symmetric (ValueError otherwise).
+      W_ij = fl(1 / (1 + max(deg_i, deg_j)))  for every edge, columns ascending
+      d_i  = fl(1 - sum_j W_ij), the sum in fp32 in ascending j
+    Not in the reference: every W of Simulator.communication_graph
+    (DIST/simulators.py:40-86) has a zero diagonal, and its doubly stochastic
+    mode is the Sinkhorn loop."""
+    n = csr.n_rows
+    if csr.n_cols != n:
+        raise ValueError(f"metropolis_weights: the pattern must be square (got {n} x {csr.n_cols})")
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(csr.rowptr, np.int64)))
+    cols = np.asarray(csr.col, np.int64)
+    off = rows != cols
+    fwd = np.unique(rows[off] * n + cols[off])  # sorted by row, then column
+    if not np.array_equal(fwd, np.unique(cols[off] * n + rows[off])):
+        raise ValueError("metropolis_weights: the sparsity pattern is not symmetric")
+    r, c = fwd // n, fwd % n
+    deg = np.bincount(r, minlength=n)
+    rowptr = np.zeros(n + 1, np.int64)
+    np.cumsum(deg, out=rowptr[1:])
+    val = np.float32(1.0) / (1 + np.maximum(deg[r], deg[c])).astype(np.float32)
+    total = np.zeros(n, np.float32)
+    for k in range(int(deg.max()) if n else 0):  # entry k of every row that has one: ascending j, one rounding each
+        has = deg > k
+        total[has] = total[has] + val[rowptr[:-1][has] + k]
+    d = (np.float32(1.0) - total).astype(np.float32)
+    return CSR(n, n, rowptr.astype(np.int32), c.astype(np.int32), val.astype(np.float32)), d
+
+
 def erdos_renyi_stochastic(n: int, p: float, generator: torch.Generator, device=None) -> torch.Tensor:
     """Dense W of a seeded undirected Erdős–Rényi G(n, p) graph under the
     reference's 'stochastic' weighting (DIST/simulators.py:65-70: G = R o A,

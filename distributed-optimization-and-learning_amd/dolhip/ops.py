@@ -31,12 +31,13 @@ __all__ = [
     "SLAB_CHUNK", "SLAB_ROWS", "csr_slab_pack", "mix_csr_slab", "slab_layout_ok", "dense_to_csr",
     "admm_ls_round_mean", "slab_variant", "SLAB_VARIANTS", "SPLIT3_FUSE_MAX_M", "SPLIT3_W_READY",
     "SPLIT3_X_ROWS_PADDED", "SPLIT3_FUSE_X", "AUTOTUNE_MIN_BYTES", "AUTOTUNE_REPS", "PM_MAX_FUSED_STEPS",
-    "FED_ALGORITHMS",
+    "FED_ALGORITHMS", "GT_MAX_AGENTS",
 ]
 
 PM_MAX_AGENTS = 8192  # dol_mix_csr_pm_f32: one p-row image (<= 32 KiB) per LDS stage
 PM_DGD_MAX_AGENTS = 4096  # dol_dgd_csr_pm_f32: X, target and momentum p-rows share a 64 KiB stage
 PM_MAX_FUSED_STEPS = 64  # DOL_PM_MAX_FUSED_STEPS: mixing steps in one dol_mix_csr_pm_steps_f32 launch
+GT_MAX_AGENTS = 4096  # dol_gt_csr_pm_f32: one quad of agents per thread; X, S and T p-rows share a stage
 RING_STEPS_VARIANTS = (1, 2, 3, 4, 5)
 PM_STAGE_ORDERS = (8, 16, 32)
 AUTOTUNE_MIN_BYTES = 1 << 30  # below this one pass is too short to be worth timing
@@ -1042,3 +1043,9 @@ from .fed_ls import fed_ls_round, fed_ls_round_mean  # noqa: E402,F401
 # on the validators above): mix_csr_pm_steps, dgd_csr_pm_steps.
 # ---------------------------------------------------------------------------
 from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noqa: E402,F401
+
+# ---------------------------------------------------------------------------
+# Gradient tracking on the parameter-major bank (gt.py, which builds on the
+# validators above and on pm_steps' square-W check): gt_csr_pm, separable_grad.
+# ---------------------------------------------------------------------------
+from .gt import gt_csr_pm, separable_grad  # noqa: E402,F401

@@ -532,6 +532,92 @@ class SeparableDGDPM:
         return float((x - x.mean(1, keepdim=True)).norm() / max(1, self.N) ** 0.5)
 
 
+class SeparableGTPM:
+    """Config 3 with gradient tracking (DIGing / NEXT) on the parameter-major
+    bank, SeparableDGDPM's sibling: every agent carries a tracker s_i of the
+    average gradient beside x_i, and one round
+
+      x_i' = sum_j W_ij x_j - lr s_i
+      s_i' = sum_j W_ij s_j + grad f_i(x_i') - grad f_i(x_i)     s_i(0) = grad f_i(x_i(0))
+
+    is one kernel and one pass over X, S and the targets (dol_gt_csr_pm_f32).
+    Where the DGD round with a constant lr leaves every agent at a biased fixed
+    point, every agent here reaches the optimum of sum_i f_i with the same
+    constant lr.  Not a reference algorithm (the reference's decentralised
+    round is consensus + local step, DIST/simulators.py:147-162).
+
+    W = plan's CSR + diag(self_weight) must be doubly stochastic with a
+    positive self weight for the method to converge: on a zero-diagonal ring
+    of even size (-1 is an eigenvalue of W) the iterates grow without bound.
+    graph.metropolis_weights builds such a W from any symmetric pattern.  lr
+    must be small against the spectral gap of W: on a random 4-regular graph
+    of 16 agents with Metropolis weights, least squares, 0.1 converges and 0.3
+    diverges (a float32 CPU simulation of this arithmetic).
+
+    XT / XO, ST / SO and TT are [P, ld] like SeparableDGDPM's matrices, with
+    the same seeded init; ST starts as ops.separable_grad(XT, TT).  Dense
+    plans and more than ops.GT_MAX_AGENTS agents are refused."""
+
+    def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
+                 self_weight=None, seed: int = 2028):
+        from . import ops
+        if plan.n_rows > ops.GT_MAX_AGENTS:
+            raise ValueError(f"the gradient-tracking round takes at most {ops.GT_MAX_AGENTS} agents")
+        if plan.kind == "dense":
+            raise ValueError("the gradient-tracking round mixes a sparse (CSR) W")
+        if objective not in ops.OBJECTIVES:
+            raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
+        self.plan, self.P, self.objective, self.lr = plan, int(P), objective, float(lr)
+        self.N = plan.n_rows
+        self.ld = (self.N + 3) // 4 * 4
+        dev = plan.device
+        self.self_weight = None
+        if self_weight is not None:
+            self.self_weight = torch.as_tensor(self_weight, dtype=torch.float32).to(dev).contiguous()
+            if self.self_weight.shape != (self.N,):
+                raise ValueError(f"self_weight: expected {self.N} weights")
+        self.XT = torch.zeros((self.P, self.ld), dtype=torch.float32, device=dev)
+        self.XO, self.ST, self.SO, self.TT = (torch.zeros_like(self.XT) for _ in range(4))
+        g = torch.Generator(device=dev).manual_seed(seed)
+        self.XT[:, :self.N].normal_(generator=g)
+        self.TT[:, :self.N].normal_(generator=g)
+        if objective == "logistic":
+            t = self.TT[:, :self.N]
+            t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+        ops.separable_grad(self.XT, self.TT, self.ST, objective)
+        self.rounds = 0
+
+    def round(self) -> None:
+        """One gradient-tracking round (one kernel); swaps XT / XO and ST / SO."""
+        from . import ops
+        p = self.plan
+        ops.gt_csr_pm(self.XT, self.ST, self.XO, self.SO, p.rowptr, p.col, p.val, self.TT,
+                      self_weight=self.self_weight, objective=self.objective, lr=self.lr, P=self.P)
+        self.XT, self.XO = self.XO, self.XT
+        self.ST, self.SO = self.SO, self.ST
+        self.rounds += 1
+
+    def params(self) -> torch.Tensor:
+        """Agent-major copy [N, P] of the current parameters (diagnostic)."""
+        return self.XT[:, :self.N].T.contiguous()
+
+    def tracker(self) -> torch.Tensor:
+        """Agent-major copy [N, P] of the gradient trackers s_i (diagnostic)."""
+        return self.ST[:, :self.N].T.contiguous()
+
+    def consensus_error(self) -> float:
+        x = self.XT[:, :self.N]
+        return float((x - x.mean(1, keepdim=True)).norm() / max(1, self.N) ** 0.5)
+
+    def distance_to_optimum(self) -> float:
+        """max over agents and coordinates of |x_ip - mean_j t_jp| (the mean in
+        fp64): least squares only, whose optimum is the mean of the targets."""
+        if self.objective != "least_squares":
+            raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
+        opt = self.TT[:, :self.N].double().mean(1, keepdim=True)
+        return float((self.XT[:, :self.N].double() - opt).abs().max())
+
+
 class TimeVaryingMLPGossip:
     """BASELINE config 5 as a first-class round: N agents, each an
     nn.Sequential(Linear(d, h), ReLU(), Linear(h, c)) row of the bank, a new

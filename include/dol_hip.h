@@ -350,6 +350,50 @@ int dol_dgd_csr_pm_steps_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t
                                 hipStream_t s);
 
 /*
+ * One gradient-tracking round (DIGing / NEXT) of BASELINE config 3 on the
+ * parameter-major bank in one pass.  Not in the reference, whose only
+ * decentralised round is consensus + local step (DIST/simulators.py:147-162;
+ * with a constant step size that settles at a biased fixed point); the mix
+ * inside is its consensus (DIST/clients.py:61-69) in dol_mix_csr_pm_f32's
+ * rounding.  XT, ST (the trackers), XO, SO are [P][ld] like XT there, TT the
+ * targets; W = W_off + diag(self_w), W_off the square CSR (0 <= col < n).
+ * For every coordinate p and agent i, all fp32, each operation rounded once:
+ *   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e)     as = the same over s
+ *   self_w != NULL:  ax = fl(ax + fl(self_w[i] * x_i));  as = fl(as + fl(self_w[i] * s_i))
+ *   x' = fma(-lr, s_i, ax)
+ *   s' = fl(fl(as + g(x', t_i)) - g(x_i, t_i))
+ *   objective 0: g = fl(x - t);   objective 1: g = -t / (1 + exp(t x))
+ * (g as dol_dgd_ring_f32's).  s starts as g(x, t): dol_separable_grad_f32.
+ * The method converges for a doubly stochastic W with a positive diagonal and
+ * lr small against its spectral gap.  The round streams X, S, T in and X', S'
+ * out once; no gradient matrix is stored.  Limits: n <= 4096; every leading
+ * dimension a multiple of 4 >= round_up(n, 4); the five matrices 16-B aligned;
+ * XT, ST, XO, SO pairwise distinct (a Jacobi update of both); objective 0 or
+ * 1.  n == 0 or P == 0: DOL_OK, nothing launched.
+ */
+int dol_gt_csr_pm_f32(const float* XT, int64_t ldx, const float* ST, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                      int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                      const float* val, const float* self_w, const float* TT, int64_t ldt, int32_t objective,
+                      float lr, hipStream_t s);
+/* dol_gt_csr_pm_f32 with the stage order per call (see dol_mix_csr_pm_ex_f32). */
+int dol_gt_csr_pm_ex_f32(const float* XT, int64_t ldx, const float* ST, int64_t lds, float* XO, int64_t ldxo,
+                         float* SO, int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                         const float* val, const float* self_w, const float* TT, int64_t ldt, int32_t objective,
+                         float lr, int32_t nseg, hipStream_t s);
+
+/*
+ * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the
+ * separable losses of dol_dgd_ring_f32 (objective 0: fl(x - t), 1:
+ * -t / (1 + exp(t x)), the same device code).  Elementwise, so it serves the
+ * agent-major and the parameter-major bank alike; it initialises the trackers
+ * of dol_gt_csr_pm_f32.  No reference counterpart (the reference's gradients
+ * come from autograd on its CNN, DIST/clients.py:34-59).  ld* >= cols; 16-B
+ * columns where every matrix is 16-B aligned with ld % 4 == 0, else scalar.
+ */
+int dol_separable_grad_f32(const float* X, int64_t ldx, const float* T, int64_t ldt, float* G, int64_t ldg,
+                           int64_t rows, int64_t cols, int32_t objective, hipStream_t s);
+
+/*
  * Fused local step of n_agents agents (rows of w/buf/g), replacing:
  *   FedProx_Client.update_model  DEC/clients.py:101-115  g' = fl(g + fl(rho*fl(w-theta)))
  *   FedAdmm_Client.update_model  DEC/clients.py:125-139  g' = fl(g + fl(alpha + fl(rho*fl(w-theta))))
