@@ -1,8 +1,8 @@
 // admm.hip — the primal/dual family on the agent-major bank: the fused prox /
 // ADMM gradient term + momentum SGD step, the dual update and its residuals,
 // the least-squares client round of FedAvg / FedProx / FedADMM (one TERMS
-// selector; alone, and fused with the server's ordered mean) and the ordered
-// sum / mean.
+// selector; alone, and fused with the server's ordered mean), the one-pass
+// SCAFFOLD round beside them, and the ordered sum / mean.
 //
 // Dropped launch variant (the default's bits; code last present at 1a824fc):
 //   DOL_ADMM_ROUND_THREADS: admm_ls_round_mean_kernel strips forced to 1024 / 256 / 64 lanes; at 8192 x 2^17
@@ -548,6 +548,163 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
   }
 }
 
+// ----------------------------------------------------------------------------
+// One SCAFFOLD server round on least squares in one pass: the client of the
+// reference's sketch (DEC/clients.py:146-170, commented out there) and the
+// server step of Karimireddy et al. 2020, Algorithm 1, on the column-strip
+// skeleton of admm_ls_round_mean_kernel (a sibling kernel, so none of that
+// template's instantiations moves).  Per sampled agent k (row a) and column:
+//   w = theta
+//   local_steps times:  g = fl(w - t_a);  g' = fl(fl(g + c) - c_a)       (:155)
+//     momentum SGD as admm_ls_lane
+//   dl   = fl(w - theta)                                                  (:162)
+//   c_a' = fl(fl(c_a - c) - fl(dl * inv))   inv = 1 / (local_steps * lr)  (:165)
+//   dc   = fl(c_a' - c_a)                                                 (:167)
+//   acc_w = k == 0 ? dl : fl(acc_w + dl);  acc_c = k == 0 ? dc : fl(acc_c + dc)
+// and once per column after the last agent
+//   theta_out = fl(theta + fl(global_lr * fl(acc_w / scale_w)))
+//   c_out     = fl(c + fl(acc_c / scale_c))
+// The control variates c_a ride in the group's dual row slot; c is read once
+// per lane like theta.  RESID: (dl^2, c_a'^2) summed as the FedADMM round's.
+// F is float or f2 (packed, an IEEE operation per half).
+// ----------------------------------------------------------------------------
+template <typename F> __device__ __forceinline__ F splat(float s) {
+  if constexpr (std::is_same<F, float>::value) return s;
+  else return F{s, s};
+}
+__device__ __forceinline__ void sq_acc(float v, double& r) { r = __builtin_fma(double(v), double(v), r); }
+__device__ __forceinline__ void sq_acc(f2 v, double& r) {
+  sq_acc(v.x, r);
+  sq_acc(v.y, r);
+}
+
+template <bool MOM, typename F>
+__device__ __forceinline__ void scaffold_ls_lane(F& w, F& b, F& ca, F& dl, F& dc, F t, F th, F c, float neg_lr,
+                                                 float mom, float inv, int steps, bool first, double& rw, double& ra) {
+  const F nlr = splat<F>(neg_lr), mu = splat<F>(mom);
+  w = th;
+  for (int k = 0; k < steps; ++k) {
+    const F g = w - t;
+    const F gg = (g + c) - ca;
+    F d = gg;
+    if constexpr (MOM) {
+      b = (first && k == 0) ? gg : b * mu + gg;
+      d = b;
+    }
+    w = __builtin_elementwise_fma(nlr, d, w);
+  }
+  dl = w - th;
+  const F cn = (ca - c) - dl * splat<F>(inv);
+  dc = cn - ca;
+  ca = cn;
+  sq_acc(dl, rw);
+  sq_acc(cn, ra);
+}
+template <bool MOM>
+__device__ __forceinline__ void scaffold_ls_lane_v(float& w, float& b, float& ca, float& dl, float& dc, float t,
+                                                   float th, float c, float neg_lr, float mom, float inv, int steps,
+                                                   bool first, double& rw, double& ra) {
+  scaffold_ls_lane<MOM, float>(w, b, ca, dl, dc, t, th, c, neg_lr, mom, inv, steps, first, rw, ra);
+}
+// f4 = two packed halves
+template <bool MOM>
+__device__ __forceinline__ void scaffold_ls_lane_v(f4& w, f4& b, f4& ca, f4& dl, f4& dc, f4 t, f4 th, f4 c,
+                                                   float neg_lr, float mom, float inv, int steps, bool first,
+                                                   double& rw, double& ra) {
+  f2 w0, w1, b0 = b.xy, b1 = b.zw, a0 = ca.xy, a1 = ca.zw, l0, l1, d0, d1;
+  scaffold_ls_lane<MOM, f2>(w0, b0, a0, l0, d0, t.xy, th.xy, c.xy, neg_lr, mom, inv, steps, first, rw, ra);
+  scaffold_ls_lane<MOM, f2>(w1, b1, a1, l1, d1, t.zw, th.zw, c.zw, neg_lr, mom, inv, steps, first, rw, ra);
+  w = f4{w0.x, w0.y, w1.x, w1.y};
+  b = f4{b0.x, b0.y, b1.x, b1.y};
+  ca = f4{a0.x, a0.y, a1.x, a1.y};
+  dl = f4{l0.x, l0.y, l1.x, l1.y};
+  dc = f4{d0.x, d0.y, d1.x, d1.y};
+}
+__device__ __forceinline__ float vscale(float a, float s) { return a * s; }
+__device__ __forceinline__ f4 vscale(f4 a, float s) { return f4{a.x * s, a.y * s, a.z * s, a.w * s}; }
+
+template <typename V, bool MOM, bool RESID, int NT, int PF = kRoundPF>
+__global__ __launch_bounds__(NT) void scaffold_ls_round_kernel(
+    float* __restrict__ W, int64_t ldw, float* __restrict__ B, int64_t ldb, float* __restrict__ CI, int64_t ldc,
+    const float* __restrict__ T, int64_t ldt, const float* theta, const float* cglob,
+    const int32_t* __restrict__ agents, const int32_t* __restrict__ first, int m, int64_t c_off, int64_t ncols_v,
+    float neg_lr, float mom, int steps, float inv, float global_lr, float* theta_out, float scale_w, float* c_out,
+    float scale_c, double* __restrict__ partial, int64_t part_off, int64_t part_stride) {
+  __shared__ double smem[NT / 64];
+  const int64_t c = int64_t(blockIdx.x) * NT + threadIdx.x;
+  const bool live = c < ncols_v;
+  if (!RESID && !live) return;
+  // dead lanes (RESID only): as admm_ls_round_mean_kernel, they compute on the
+  // last real column, their row stores go out of range and their sums are dropped
+  const int64_t cc = live ? c : ncols_v - 1;
+  const uint32_t voff = live ? uint32_t(c) * uint32_t(sizeof(V)) : kOOB;
+  auto st = [&](V v, float* base, int64_t ld, int64_t row) {
+    st_row(v, base + row * ld + c_off, std::min<int64_t>((ld - c_off) * 4, 0x7ffffff0), voff);
+  };
+  auto cptr = [&](const float* base, int64_t ld, int64_t row) {
+    return reinterpret_cast<const V*>(base + row * ld + c_off) + cc;
+  };
+  auto row_of = [&](int k) -> int64_t {  // agent k's row; k past m: the last agent's (a harmless re-read)
+    k = min(k, m - 1);
+    return agents ? agents[k] : k;
+  };
+  // theta_out may be theta and c_out may be c: each lane reads its column here and writes it last
+  const V th = *cptr(theta, 0, 0);
+  const V cg = *cptr(cglob, 0, 0);
+  V acc_w = vzero(th), acc_c = vzero(th);
+  double rw = 0.0, ra = 0.0;
+  using Grp = RoundGrp<V, PF, true>;  // a[] carries the control variates c_a
+  auto load = [&](Grp& g, int k0) {  // agents k0 .. k0 + PF - 1, unconditionally (rows clamped)
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      g.row[u] = row_of(k0 + u);
+      g.t[u] = ldnt(cptr(T, ldt, g.row[u]));
+      g.a[u] = ldnt(cptr(CI, ldc, g.row[u]));
+      if constexpr (MOM) g.b[u] = ldnt(cptr(B, ldb, g.row[u]));
+    }
+  };
+  auto run = [&](Grp& g, int u, int k) {  // agent k = group slot u: its steps, stores, and the two chains
+    const bool fst = first ? first[k] != 0 : false;
+    V w, dl, dc, bu = MOM ? g.b[u] : vzero(th), au = g.a[u];
+    double rwu = 0.0, rau = 0.0;
+    scaffold_ls_lane_v<MOM>(w, bu, au, dl, dc, g.t[u], th, cg, neg_lr, mom, inv, steps, fst, rwu, rau);
+    st(w, W, ldw, g.row[u]);
+    st(au, CI, ldc, g.row[u]);
+    if constexpr (MOM) st(bu, B, ldb, g.row[u]);
+    rw += live ? rwu : 0.0;
+    ra += live ? rau : 0.0;
+    acc_w = k == 0 ? dl : vadd(acc_w, dl);
+    acc_c = k == 0 ? dc : vadd(acc_c, dc);
+  };
+  const int ng = (m + PF - 1) / PF;  // groups; all but the last are full
+  Grp nxt, cur;
+  load(nxt, 0);
+  for (int gi = 0; gi + 1 < ng; ++gi) {  // straight-line body: the same memory ops every trip
+    cur = nxt;
+    load(nxt, (gi + 1) * PF);      // the next group's loads fly during this group's steps
+#pragma unroll
+    for (int u = 0; u < PF; ++u) run(cur, u, gi * PF + u);
+  }
+#pragma unroll
+  for (int u = 0; u < PF; ++u) {   // the last group (maybe partial)
+    const int k = (ng - 1) * PF + u;
+    if (k < m) run(nxt, u, k);
+  }
+  if (live) {
+    *(reinterpret_cast<V*>(theta_out + c_off) + c) = vadd(th, vscale(vdiv(acc_w, scale_w), global_lr));
+    *(reinterpret_cast<V*>(c_out + c_off) + c) = vadd(cg, vdiv(acc_c, scale_c));
+  }
+  if constexpr (RESID) {
+    const double sw = block_sum_f64_nt<NT>(rw, smem);
+    __syncthreads();
+    const double sa = block_sum_f64_nt<NT>(ra, smem);
+    if (threadIdx.x == 0) {
+      partial[part_off + blockIdx.x] = sw;
+      partial[part_stride + part_off + blockIdx.x] = sa;
+    }
+  }
+}
+
 // The least-squares client round of the three algorithms; nm names the entry
 // point in the messages.  alg == DOL_FED_ADMM is dol_admm_ls_round_f32 as ever.
 int fed_ls_round(const char* nm, float* w, int64_t ldw, float* buf, int64_t ldb, float* alpha, int64_t lda,
@@ -823,6 +980,59 @@ int dol_admm_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, f
   return fed_ls_round_mean("dol_admm_ls_round_mean_f32", w, ldw, buf, ldb, alpha, lda, target, ldt, theta, agents,
                            first, m, P, DOL_FED_ADMM, rho, lr, momentum, local_steps, theta_out, scale, resid_total,
                            work, s);
+}
+
+int dol_scaffold_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* ci, int64_t ldc,
+                              const float* target, int64_t ldt, const float* theta, const float* c,
+                              const int32_t* agents, const int32_t* first, int32_t m, int64_t P, float lr,
+                              float momentum, int32_t local_steps, float inv_steps_lr, float global_lr,
+                              float* theta_out, float scale_w, float* c_out, float scale_c, double* resid_total,
+                              void* work, hipStream_t s) {
+  const char* nm = "dol_scaffold_ls_round_f32";
+  DOL_DIMS_OK(nm, ldw, ldb, ldc, ldt, P);
+  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the chains start at the first sampled client)", nm);
+  if (P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (local_steps < 1) return fail(DOL_EINVAL, "%s: local_steps must be >= 1", nm);
+  if (!(scale_w > 0.0f) || !(scale_c > 0.0f)) return fail(DOL_EINVAL, "%s: scale_w and scale_c must be > 0", nm);
+  const bool mom = momentum != 0.0f;
+  if (P > 0 && (!w || !ci || !target || !theta || !c || !theta_out || !c_out || (mom && !buf)))
+    return fail(DOL_EINVAL, "%s: null pointer", nm);
+  for (const float* out : {static_cast<const float*>(theta_out), static_cast<const float*>(c_out)})
+    if (out && (out == w || out == ci || out == target || (mom && out == buf)))
+      return fail(DOL_EINVAL, "%s: %s aliases the rows", nm, out == theta_out ? "theta_out" : "c_out");
+  if (theta_out && theta_out == c_out) return fail(DOL_EINVAL, "%s: theta_out and c_out alias", nm);
+  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
+  if (ldw < P || ldc < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  if (P == 0) {  // nothing to do but to zero the totals
+    if (!resid_total) { g_err[0] = '\0'; return DOL_OK; }
+    (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
+    return check_launch(nm);
+  }
+  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(ci, ldc) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
+                      row_vec_ok(c, 0) && row_vec_ok(theta_out, 0) && row_vec_ok(c_out, 0) &&
+                      (!mom || row_vec_ok(buf, ldb));
+  const ColSplit cs = split_cols(P, vec_ok);
+  // the strip choice of fed_ls_round_mean: 1024 lanes at one workgroup per CU and up, else 256
+  const int n_cu = n_cus() > 0 ? n_cus() : 256;
+  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
+  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
+  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
+  const int64_t nb = nb4 + nbt;
+  double* partial = static_cast<double*>(work);
+  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
+    dispatch([&](auto mc, auto rc, auto ntc) {
+      hipLaunchKernelGGL((scaffold_ls_round_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
+                                                   decltype(ntc)::value>),
+                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, ci, ldc, target, ldt,
+                         theta, c, agents, first, m, c_off, ncols, -lr, momentum, local_steps, inv_steps_lr, global_lr,
+                         theta_out, scale_w, c_out, scale_c, partial, part_off, nb);
+    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt});
+  };
+  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
+  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
+  if (resid_total) hipLaunchKernelGGL(resid_reduce_kernel, dim3(2), dim3(kThreads), 0, s, partial, nb, resid_total);
+  return check_launch(nm);
 }
 
 int dol_ordered_sum_f32(const float* W, int64_t ldw, const int32_t* order, int32_t m, int64_t P,

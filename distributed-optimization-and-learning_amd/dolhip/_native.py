@@ -56,6 +56,8 @@ SIGNATURES = {
                              _f32, _f32, _i32, _ptr, _ptr, _ptr, _ptr],
     "dol_fed_ls_round_mean_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _i32, _i64, _i32,
                                   _f32, _f32, _f32, _i32, _ptr, _f32, _ptr, _ptr, _ptr],
+    "dol_scaffold_ls_round_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i64,
+                                  _f32, _f32, _i32, _f32, _f32, _ptr, _f32, _ptr, _f32, _ptr, _ptr, _ptr],
     "dol_ordered_mean_f32": [_ptr, _i64, _ptr, _i32, _i64, _ptr, _ptr],
     "dol_ordered_sum_f32": [_ptr, _i64, _ptr, _i32, _i64, _ptr, _ptr, _f32, _ptr],
     "dol_stream_copy_f32": [_ptr, _ptr, _i64, _ptr],

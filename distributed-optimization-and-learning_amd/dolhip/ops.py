@@ -1039,6 +1039,13 @@ def mlp_step(w: torch.Tensor, X: torch.Tensor, y: torch.Tensor, d: int, h: int, 
 from .fed_ls import fed_ls_round, fed_ls_round_mean  # noqa: E402,F401
 
 # ---------------------------------------------------------------------------
+# The SCAFFOLD least-squares round beside them (scaffold.py, on the same
+# validators; its own entry point, not a fourth FED_ALGORITHMS value):
+# scaffold_ls_round.
+# ---------------------------------------------------------------------------
+from .scaffold import scaffold_ls_round  # noqa: E402,F401
+
+# ---------------------------------------------------------------------------
 # Multi-step consensus on the parameter-major bank (pm_steps.py, which builds
 # on the validators above): mix_csr_pm_steps, dgd_csr_pm_steps.
 # ---------------------------------------------------------------------------

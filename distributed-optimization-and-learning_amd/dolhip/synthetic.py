@@ -436,6 +436,113 @@ class SeparableFedProx(SeparableADMM):
         super().__init__(n_agents, P, algorithm="fedprox", **kw)
 
 
+class SeparableScaffold:
+    """SCAFFOLD on the separable least-squares objective f_k(w) = 1/2 ||w - t_k||^2
+    over stacked agent rows: the server round of SeparableADMM with the
+    reference's fourth client, the commented-out Scaffold_Client sketch
+    (DEC/clients.py:146-170), and the server step of Karimireddy et al. 2020,
+    Algorithm 1, which the reference never wrote.  One round, in one pass
+    (dol_scaffold_ls_round_f32):
+      m = max(int(frac * N), 1); order = np.random.choice(range(N), m, replace=False)
+      every sampled client: w <- theta, local_steps x momentum SGD on the
+        gradient corrected by c - c_k (:155), then c_k <- c_k - c - (w - theta)
+        / (local_steps * lr) (:162-165)
+      theta <- theta + global_lr * mean over the sampled of (w - theta)
+      c     <- c + (1 / N) * sum over the sampled of the change of c_k
+    The control variates remove the client drift and the sampling error that
+    keep FedAvg's theta moving under frac < 1 and that bias FedADMM's fixed
+    point (SeparableADMM.fixed_point): theta reaches optimum() = mean_k t_k.
+
+    A standalone class, not an `algorithm=` of SeparableADMM: there is a second
+    server vector, the server step is not an ordered mean of the rows, and no
+    two-kernel or sharded variant exists (single process only).  Targets and
+    theta are seeded as SeparableADMM's; c_k and c start at zero; the sampling
+    replays the reference's np.random.choice stream; each client's momentum
+    buffer persists across rounds (`mom_started`).  `history` has
+    SeparableADMM's keys: primal_resid_sq = sum over the sampled clients of
+    ||w_k - theta||^2 (pre-round theta), dual_sq = that of ||c_k||^2.
+    `round_fn` injects a CPU checker with ops.scaffold_ls_round's signature."""
+
+    def __init__(self, n_agents: int, P: int, lr: float = 0.1, momentum: float = 0.5, local_steps: int = 1,
+                 frac: float = 1.0, global_lr: float = 1.0, seed: int = 2028, device=None, metrics: bool = True,
+                 round_fn=None):
+        import numpy as np
+        import torch.distributed as dist
+
+        from . import ops
+        from .bank import row_stride
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("SeparableScaffold runs in one process (no sharded SCAFFOLD round)")
+        if int(local_steps) < 1:
+            raise ValueError("local_steps must be >= 1")
+        self.N, self.P = int(n_agents), int(P)
+        self.lr, self.mu, self.local_steps = float(lr), float(momentum), int(local_steps)
+        self.global_lr = float(global_lr)
+        self.m = max(int(frac * self.N), 1)
+        self.metrics = metrics
+        self.device = dev = torch.device(device) if device is not None else torch.device("cuda")
+        self._round = round_fn if round_fn is not None else ops.scaffold_ls_round
+        self.rs = np.random.RandomState(seed)  # the reference's np.random.choice stream (setup_seed)
+        ld = row_stride(max(self.P, 1))
+        self.w = torch.zeros(self.N, ld, dtype=torch.float32, device=dev)
+        self.ci = torch.zeros_like(self.w)
+        self.target = torch.empty_like(self.w)
+        self.mom = torch.zeros_like(self.w) if self.mu != 0.0 else None
+        for k in range(self.N):  # SeparableADMM's per-row seeds
+            g = torch.Generator(device=dev).manual_seed(seed * 1000003 + k + 1)
+            self.target[k, :self.P].normal_(generator=g)
+        g = torch.Generator(device=dev).manual_seed(seed)
+        self.theta = torch.zeros(ld, dtype=torch.float32, device=dev)
+        self.theta[:self.P].copy_(torch.empty(self.P, dtype=torch.float32, device=dev).normal_(generator=g))
+        self.c =torch.zeros_like(self.theta)
+        self.mom_started = np.zeros(self.N, dtype=bool)
+        self.rounds = 0
+        self._pending = []  # per-round device metrics, read lazily (no sync on the round path)
+        self._history = []
+
+    def sample(self):
+        """The sampled clients of the next round, in the reference's order."""
+        return self.rs.choice(range(self.N), self.m, replace=False)
+
+    def round(self, order=None) -> None:
+        import numpy as np
+        order = np.asarray(self.sample() if order is None else order, dtype=np.int64)
+        if order.size < 1 or order.min() < 0 or order.max() >= self.N or len(set(order.tolist())) != order.size:
+            raise ValueError(f"order must be distinct agent ids in [0, {self.N})")
+        dev = self.device
+        rows = torch.as_tensor(order, dtype=torch.int32, device=dev)
+        first = None
+        if self.mom is not None:
+            first = torch.as_tensor(~self.mom_started[order], dtype=torch.int32, device=dev)
+        s = torch.zeros(2, dtype=torch.float64, device=dev) if self.metrics else None
+        # theta and c are stepped in place: each column is read before it is written
+        self._round(self.w, self.ci, self.target, self.theta, self.c, agents=rows, first=first, buf=self.mom,
+                    lr=self.lr, momentum=self.mu, local_steps=self.local_steps, global_lr=self.global_lr,
+                    theta_out=self.theta, c_out=self.c, n_total=self.N, resid_total=s, P=self.P, validate=False)
+        if self.mom is not None:
+            self.mom_started[order] = True
+        if self.metrics:
+            self._pending.append((self.rounds, s))
+        self.rounds += 1
+
+    @property
+    def history(self):
+        """Per-round metrics: {"round", "primal_resid_sq", "dual_sq"} (sums over the sampled clients)."""
+        for r, s in self._pending:
+            v = s.cpu().tolist()
+            self._history.append({"round": r, "primal_resid_sq": v[0], "dual_sq": v[1]})
+        self._pending = []
+        return self._history
+
+    def optimum(self) -> torch.Tensor:
+        """mean_k t_k in fp64 (the minimiser of sum_k f_k)."""
+        return self.target[:, :self.P].double().sum(0) / self.N
+
+    def distance_to_optimum(self) -> float:
+        """||theta - mean_k t_k|| / sqrt(P)."""
+        return float((self.theta[:self.P].double() - self.optimum()).norm() / self.P ** 0.5)
+
+
 class SeparableDGDPM:
     """Config 3 on the parameter-major bank: the round of SeparableDGD (same
     objectives, same round order, bit-identical values) with every state

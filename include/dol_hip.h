@@ -560,6 +560,45 @@ int dol_fed_ls_round_mean_f32(float* w, int64_t ldw, float* buf, int64_t ldb, fl
                               double* resid_total, void* work, hipStream_t s);
 
 /*
+ * One SCAFFOLD server round on the same least-squares objective, in one pass.
+ * The client is the reference's commented-out sketch, Scaffold_Client
+ * (DEC/clients.py:146-170), with the CNN gradient swapped for the exact
+ * least-squares one; the server step, which the reference does not have, is
+ * Karimireddy et al. 2020, Algorithm 1, with a global step size.  For the
+ * sampled agent k (row a = agents[k]; agents NULL: a = k), per column:
+ *   w = theta
+ *   local_steps times:  g = fl(w - t_a)
+ *     g' = fl(fl(g + c) - c_a)                         (:155, grad + alpha_server - alpha)
+ *     momentum != 0: buf = (first[k] && step 0) ? g' : fl(fl(buf*momentum) + g'); d = buf
+ *     momentum == 0: d = g'
+ *     w = fma(-lr, d, w)
+ *   dl   = fl(w - theta)                               (:162, local_sum)
+ *   c_a' = fl(fl(c_a - c) - fl(dl * inv_steps_lr))     (:165)
+ *   dc   = fl(c_a' - c_a)                              (:167, control_update)
+ *   acc_w = k == 0 ? dl : fl(acc_w + dl);  acc_c = k == 0 ? dc : fl(acc_c + dc)
+ * and once per column after the last client
+ *   theta_out = fl(theta + fl(global_lr * fl(acc_w / scale_w)))   (scale_w = m: the paper's mean)
+ *   c_out     = fl(c + fl(acc_c / scale_c))                       (scale_c = N, ALL clients)
+ * inv_steps_lr is 1 / (local_steps * lr) as the caller rounds it (:164; the
+ * Python layer computes it in double and rounds once).  ci: the clients'
+ * control variates, [rows] x ldc, read and written for the sampled rows only;
+ * c: the server's, [P].  w is only written; rows not sampled are not touched.
+ * agents DISTINCT, m >= 1, local_steps >= 1, both scales > 0, P < 2^29.
+ * theta_out may alias theta and c_out may alias c (each column is read before
+ * it is written); neither may alias a row matrix or the other output.
+ * resid_total (nullable, fp64 [2]): [0] the round's sum over the agents of
+ * ||dl||^2 (the client drift), [1] that of ||c_a'||^2, in a fixed reduction
+ * order; it needs `work` of dol_admm_ls_round_mean_workspace_bytes(P) bytes.
+ * P == 0 only zeroes resid_total.  Nothing allocates or synchronises.
+ */
+int dol_scaffold_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, float* ci, int64_t ldc,
+                              const float* target, int64_t ldt, const float* theta, const float* c,
+                              const int32_t* agents, const int32_t* first, int32_t m, int64_t P, float lr,
+                              float momentum, int32_t local_steps, float inv_steps_lr, float global_lr,
+                              float* theta_out, float scale_w, float* c_out, float scale_c, double* resid_total,
+                              void* work, hipStream_t s);
+
+/*
  * Ordered uniform average, replacing Server.average_weights
  *   DEC/servers.py:42-48:  acc = w[order[0]]; acc = fl(acc + w[order[k]]) k=1..m-1;
  *                          theta = fl(acc / (float)m)
