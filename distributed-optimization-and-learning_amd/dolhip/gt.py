@@ -1,8 +1,10 @@
-"""Gradient tracking (DIGing / NEXT) for BASELINE config 3 on the
-parameter-major bank: one round in one HBM pass (dol_gt_csr_pm_f32) and the
-device gradient of the separable losses (dol_separable_grad_f32) that starts
-the trackers.  ops re-exports both calls as ops.gt_csr_pm /
-ops.separable_grad.
+"""Gradient tracking (DIGing / NEXT) for BASELINE config 3: one round in one
+HBM pass on the parameter-major bank (dol_gt_csr_pm_f32, any sparse W, at most
+ops.GT_MAX_AGENTS agents) and on the agent-major ring (dol_gt_ring_f32, any
+number of agents, and the blocks of a sharded ring through its halo form), and
+the device gradient of the separable losses (dol_separable_grad_f32) that
+starts the trackers.  ops re-exports the calls as ops.gt_csr_pm / ops.gt_ring
+/ ops.separable_grad.
 
   x_i' = sum_j W_ij x_j - lr s_i
   s_i' = sum_j W_ij s_j + grad f_i(x_i') - grad f_i(x_i)       s_i(0) = grad f_i(x_i(0))
@@ -15,6 +17,7 @@ validators of ops.py (_check_rows, _check_csr, _check_array) and pm_steps'
 square-W check, plus the four stated here: a known objective, at most
 ops.GT_MAX_AGENTS agents, four distinct state matrices and a self-weight
 vector of n floats; tests/test_gt_host.py pins them without a launch.
+gt_ring's own rules are in its docstring and in tests/test_gt_ring_host.py.
 """
 from __future__ import annotations
 
@@ -70,6 +73,52 @@ def gt_csr_pm(XT: torch.Tensor, ST: torch.Tensor, XO: torch.Tensor, SO: torch.Te
     _native.call("dol_gt_csr_pm_ex_f32", XT.data_ptr(), ldx, ST.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(),
                  ldso, n, P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
                  _ops._ptr(self_weight), TT.data_ptr(), ldt, obj, float(lr), int(nseg), _ops._stream(XT))
+    return XO, SO
+
+
+def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, w_prev: torch.Tensor,
+            w_next: torch.Tensor, target: torch.Tensor, self_weight: Optional[torch.Tensor] = None,
+            objective: str = "least_squares", lr: float = 0.01, halos=None, P: Optional[int] = None,
+            n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gt_csr_pm's round on the agent-major ring (dol_gt_ring_f32), for any
+    number of agents and for the blocks of a sharded ring: X the parameters, S
+    the trackers, target the targets, [>= n_rows, >= P] like mix_ring's X; XO /
+    SO receive x' / s'.  W = the ring stencil (w_prev, w_next [n_rows], as
+    mix_ring) + diag(self_weight).  Per coordinate
+      ax = fl(fl(+0 + fl(w_prev x[r-1])) + fl(w_next x[r+1])), as the same over s
+      ax = fl(ax + fl(d_r x_r)), as = fl(as + fl(d_r s_r))     with self_weight
+      x' = fma(-lr, s_r, ax);  s' = fl(fl(as + g(x', t_r)) - g(x_r, t_r))
+    the bits of gt_csr_pm on the ring's CSR.  halos: (x_prev, x_next, s_prev,
+    s_next), the rows of X and S before and after the local block ([>= P]
+    each), or None for the wrap-around ring inside X and S.  The rules of this
+    op: a known objective; the four state matrices distinct (a Jacobi update
+    of both); all four halos or None; without halos at least 3 rows; a
+    self-weight vector of n_rows floats.  Returns (XO, SO)."""
+    obj = _check_objective("gt_ring", objective)
+    P = X.shape[1] if P is None else P
+    n = X.shape[0] if n_rows is None else n_rows
+    state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
+    for i, (na, a) in enumerate(state):
+        for nb, b in state[i + 1:]:
+            if a is b or a.data_ptr() == b.data_ptr():
+                raise ValueError(f"gt_ring: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+    for nm, w in (("w_prev", w_prev), ("w_next", w_next)) + ((("self_weight", self_weight),) if self_weight is not None
+                                                              else ()):
+        _ops._check_array(nm, w, torch.float32, n, X.device)
+    if halos is not None:
+        if len(halos) != 4 or any(h is None for h in halos):
+            raise ValueError("gt_ring: halos are (x_prev, x_next, s_prev, s_next), all four or None")
+    elif n < 3:
+        raise ValueError("gt_ring: a wrap-around ring needs >= 3 rows (pass halos, or use gt_csr_pm)")
+    ldx, ld_s, ldxo, ldso, ldt = (
+        _ops._check_rows(nm, t, P, n, f"{nm}: expected >= {n} rows on {{}}", 0, X.device)
+        for nm, t in state + (("target", target),))
+    for nm, h in zip(("x_prev", "x_next", "s_prev", "s_next"), halos or ()):
+        _ops._check_vec(f"halos {nm}", h, P, X.device)
+    hp = [None] * 4 if halos is None else [h.data_ptr() for h in halos]
+    _native.call("dol_gt_ring_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,
+                 P, hp[0], hp[1], hp[2], hp[3], w_prev.data_ptr(), w_next.data_ptr(), _ops._ptr(self_weight),
+                 target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
     return XO, SO
 
 

@@ -694,6 +694,18 @@ class SeparableGTPM:
         ops.separable_grad(self.XT, self.TT, self.ST, objective)
         self.rounds = 0
 
+    @classmethod
+    def from_agent_major(cls, prob: "SeparableGT") -> "SeparableGTPM":
+        """The problem of a SeparableGT on this bank: its plan, self weights and
+        lr, and its current parameters, trackers and targets transposed (the
+        two layouts draw their seeded init in different element orders)."""
+        from . import ops
+        self = cls(prob.plan, prob.P, prob.objective, prob.lr, self_weight=prob.self_weight)
+        for src, dst in ((prob.params(), self.XT), (prob.tracker(), self.ST), (prob.targets(), self.TT)):
+            ops.transpose(src, dst, prob.N, prob.P)
+        self.rounds = prob.rounds
+        return self
+
     def round(self) -> None:
         """One gradient-tracking round (one kernel); swaps XT / XO and ST / SO."""
         from . import ops
@@ -723,6 +735,103 @@ class SeparableGTPM:
             raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
         opt = self.TT[:, :self.N].double().mean(1, keepdim=True)
         return float((self.XT[:, :self.N].double() - opt).abs().max())
+
+
+def ring_gt_weights(ring_csr):
+    """(w_prev, w_next, w_self), float32 [n] each, as ops.gt_ring and
+    SeparableGT take them: graph.metropolis_weights on the pattern of
+    `ring_csr` (row i = {i - 1, i + 1} mod n, n >= 3; its values are not
+    used), the off-diagonal part through CSR.ring_weights.  On a ring every
+    degree is 2: each edge weighs fl(1/3) and w_self = fl(1 - fl(1/3 + 1/3)),
+    a symmetric doubly stochastic W with a positive diagonal."""
+    from .graph import metropolis_weights
+    w_off, d = metropolis_weights(ring_csr)
+    ring = w_off.ring_weights()
+    if ring is None:
+        raise ValueError("ring_gt_weights: the pattern is not a ring (row i = {i - 1, i + 1} mod n, n >= 3)")
+    return ring[0], ring[1], d
+
+
+class SeparableGT:
+    """Config 3 with gradient tracking on the agent-major ring, SeparableGTPM's
+    sibling on SeparableDGD's bank: the same round (see SeparableGTPM), one
+    kernel and one pass over X, S and the targets (dol_gt_ring_f32), for any
+    number of agents -- the parameter-major round stops at ops.GT_MAX_AGENTS.
+    Not a reference algorithm.
+
+    plan must be a ring plan (plan.kind == "ring": its w_prev / w_next are the
+    stencil); W = that stencil + diag(self_weight) must be doubly stochastic
+    with a positive diagonal, which ring_gt_weights gives.  lr must be small
+    against the spectral gap of W, which shrinks as 1 / n^2 on a ring: on 9
+    agents with Metropolis weights, least squares, 0.1 converges in 200 rounds
+    and 0.3 diverges; 33 agents need far more rounds (a float32 CPU simulation
+    of this arithmetic).
+
+    The bank holds x / y (parameters in and out), s / s_out (trackers) and
+    target, with SeparableDGD's seeded init; s starts as ops.separable_grad(x,
+    target).  The parameter-major draw of SeparableGTPM is another element
+    order: SeparableGTPM.from_agent_major makes the same problem there."""
+
+    def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
+                 self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
+        from . import ops
+        if plan.kind != "ring":
+            raise ValueError(f"SeparableGT runs on a ring plan (got kind {plan.kind!r}); SeparableGTPM takes any "
+                             f"sparse W of up to {ops.GT_MAX_AGENTS} agents")
+        if objective not in ops.OBJECTIVES:
+            raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
+        self.plan, self.objective, self.lr = plan, objective, float(lr)
+        self.N = plan.n_rows
+        dev = plan.device
+        self.self_weight = None
+        if self_weight is not None:
+            self.self_weight = torch.as_tensor(self_weight, dtype=torch.float32).to(dev).contiguous()
+            if self.self_weight.shape != (self.N,):
+                raise ValueError(f"self_weight: expected {self.N} weights")
+        self.bank = bank if bank is not None else AgentBank(self.N, P, dev)
+        self.P = self.bank.P
+        g = torch.Generator(device=dev).manual_seed(seed)
+        self.bank.buffer("x").normal_(generator=g)
+        t = self.bank.buffer("target")
+        t.normal_(generator=g)
+        if objective == "logistic":  # t = label (+-1) * feature
+            t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+        for name in ("y", "s", "s_out"):
+            self.bank.buffer(name, zero=True)
+        ops.separable_grad(self.bank.rows("x"), self.bank.rows("target"), self.bank.rows("s"), objective)
+        self.rounds = 0
+
+    def round(self) -> None:
+        """One gradient-tracking round (one kernel); swaps x / y and s / s_out."""
+        from . import ops
+        b, p = self.bank, self.plan
+        ops.gt_ring(b.buffer("x"), b.buffer("s"), b.buffer("y"), b.buffer("s_out"), p.w_prev, p.w_next,
+                    b.buffer("target"), self_weight=self.self_weight, objective=self.objective, lr=self.lr, P=self.P,
+                    n_rows=self.N)
+        b.swap("x", "y")
+        b.swap("s", "s_out")
+        self.rounds += 1
+
+    def params(self) -> torch.Tensor:
+        return self.bank.rows("x")
+
+    def tracker(self) -> torch.Tensor:
+        return self.bank.rows("s")
+
+    def targets(self) -> torch.Tensor:
+        return self.bank.rows("target")
+
+    def consensus_error(self) -> float:
+        x = self.params()
+        return float((x - x.mean(0, keepdim=True)).norm() / max(1, x.shape[0]) ** 0.5)
+
+    def distance_to_optimum(self) -> float:
+        """max over agents and coordinates of |x_ip - mean_j t_jp| (the mean in
+        fp64): least squares only, whose optimum is the mean of the targets."""
+        if self.objective != "least_squares":
+            raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
+        opt = self.targets().double().mean(0, keepdim=True)
+        return float((self.params().double() - opt).abs().max())
 
 
 class TimeVaryingMLPGossip:

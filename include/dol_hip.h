@@ -382,6 +382,37 @@ int dol_gt_csr_pm_ex_f32(const float* XT, int64_t ldx, const float* ST, int64_t 
                          float lr, int32_t nseg, hipStream_t s);
 
 /*
+ * One gradient-tracking round (DIGing / NEXT) of BASELINE config 3 on the
+ * agent-major ring in one pass: dol_gt_csr_pm_f32's round in dol_mix_ring_f32's
+ * layout, for the row counts and the sharded blocks the parameter-major bank
+ * does not take.  Not in the reference: it replaces the consensus + local step
+ * round of DIST/simulators.py:147-162 (a biased fixed point under a constant
+ * step size); the mix inside is its consensus (DIST/clients.py:61-69) in
+ * dol_mix_ring_f32's rounding.  X (parameters), S (trackers), XO, SO and target
+ * are row matrices of n_rows rows; W = the ring stencil + diag(w_self).  For
+ * every row r and column c, all fp32, each operation rounded once:
+ *   ax = fl(fl(+0 + fl(w_prev[r]*x[r-1])) + fl(w_next[r]*x[r+1]))     as = the same over s
+ *   w_self != NULL:  ax = fl(ax + fl(w_self[r]*x[r]));  as = fl(as + fl(w_self[r]*s[r]))
+ *   x' = fma(-lr, s[r], ax)
+ *   s' = fl(fl(as + g(x', t[r])) - g(x[r], t[r]))        g as dol_separable_grad_f32
+ * the bits of dol_gt_csr_pm_f32 on the ring's CSR with the same self weights.
+ * Row -1 / row n_rows of X and S are x_halo_prev / x_halo_next and s_halo_prev
+ * / s_halo_next ([P] each; all four or none), or the wrap-around rows of X and
+ * S themselves without halos (n_rows >= 3 then; with halos n_rows >= 1, one row
+ * mixing from both halos).  X, S, XO, SO pairwise distinct (a Jacobi update of
+ * both); every ld >= P; objective 0 or 1.  16-B columns where the five
+ * matrices and the halos are 16-B aligned with ld % 4 == 0, else scalar.  The
+ * round streams X, S, target in and XO, SO out once.  n_rows == 0 or P == 0:
+ * DOL_OK, nothing launched.  Stream-ordered; allocates nothing; does not
+ * synchronise.
+ */
+int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                    int64_t ldso, int32_t n_rows, int64_t P, const float* x_halo_prev, const float* x_halo_next,
+                    const float* s_halo_prev, const float* s_halo_next, const float* w_prev, const float* w_next,
+                    const float* w_self /* nullable */, const float* target, int64_t ldt, int32_t objective,
+                    float lr, hipStream_t s);
+
+/*
  * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the
  * separable losses of dol_dgd_ring_f32 (objective 0: fl(x - t), 1:
  * -t / (1 + exp(t x)), the same device code).  Elementwise, so it serves the
