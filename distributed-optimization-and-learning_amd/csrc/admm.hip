@@ -4,10 +4,22 @@
 // selector; alone, and fused with the server's ordered mean), the one-pass
 // SCAFFOLD round beside them, and the ordered sum / mean.
 //
+// What the rounds share is stated once: the local-step lanes are F-generic
+// (float, or f2 packed; an f4 column is two f2 halves), and the one-pass
+// rounds have one host launch plan (launch_strips) and one set of shared
+// argument rules (check_strip_round).  The column-strip walk itself is still
+// written out in both one-pass kernels, admm_ls_round_mean_kernel and
+// scaffold_ls_round_kernel: a shared device-side skeleton taking the step, the
+// chain and the epilogue as callables did not reproduce their code (DESIGN.md,
+// "One strip walk: tried, left out"), so a fix to the dead-lane rule or the
+// prefetch pipeline is made in both.
+//
 // Dropped launch variant (the default's bits; code last present at 1a824fc):
 //   DOL_ADMM_ROUND_THREADS: admm_ls_round_mean_kernel strips forced to 1024 / 256 / 64 lanes; at 8192 x 2^17
 //     18.6 / 7.4 / 7.65 ms, and 5.15 for the two-kernel round (profiles/r06c_admm_narrow_ab.jsonl).
 #include <algorithm>
+#include <initializer_list>
+#include <utility>
 
 #include "dol_launch.h"
 
@@ -99,6 +111,7 @@ __global__ __launch_bounds__(kThreads) void prox_grad_kernel(
 // ----------------------------------------------------------------------------
 constexpr int kDualIters = 4;
 
+template <int NT = kThreads>
 __device__ __forceinline__ double block_sum_f64(double v, double* smem) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -107,7 +120,7 @@ __device__ __forceinline__ double block_sum_f64(double v, double* smem) {
   __syncthreads();
   double s = 0.0;
   if (threadIdx.x == 0) {
-    for (int i = 0; i < kThreads / 64; ++i) s += smem[i];
+    for (int i = 0; i < NT / 64; ++i) s += smem[i];
   }
   return s;
 }
@@ -212,72 +225,56 @@ __global__ __launch_bounds__(kThreads) void resid_reduce_kernel(const double* __
 //   1 FedProx  g' = fl(g + fl(rho * fl(w - theta)))    (:101-115)
 //   2 FedADMM  the above, dual ascent included          (:125-144)
 // update_duals is a no-op for 0 and 1 (:58-59): a and ra are then not touched.
-template <bool MOM, int TERMS = 2>
-__device__ __forceinline__ void admm_ls_lane(float& w, float& b, float& a, float t, float th, float rho,
-                                             float neg_lr, float mom, int steps, bool first, double& rw,
-                                             double& ra) {
-  w = th;
-  for (int k = 0; k < steps; ++k) {
-    const float g = w - t;
-    float gg = g;
-    if constexpr (TERMS == 2) gg = g + (a + rho * (w - th));
-    if constexpr (TERMS == 1) gg = g + rho * (w - th);
-    float d = gg;
-    if constexpr (MOM) {
-      b = (first && k == 0) ? gg : b * mom + gg;
-      d = b;
-    }
-    w = __builtin_fmaf(neg_lr, d, w);
-  }
-  const float dl = w - th;
-  if constexpr (TERMS == 2) a = a + rho * dl;
-  // the product of two floats is exact in double, so fma == the reference's
-  // separately rounded rw + d*d, one instruction fewer
-  rw = __builtin_fma(double(dl), double(dl), rw);
-  if constexpr (TERMS == 2) ra = __builtin_fma(double(a), double(a), ra);
-}
-
-// The same lane on two columns at once: packed fp32 (v_pk_add / v_pk_mul /
-// v_pk_fma_f32 on gfx950, each an IEEE operation per half), same rounding per
-// element as admm_ls_lane.  At 10 local steps the round runs ~70 fp32 ops per
-// element: unpacked that is ~60 % of the HBM time in VALU issue.
+// F is float or f2: two columns at once in packed fp32 (v_pk_add / v_pk_mul /
+// v_pk_fma_f32 on gfx950, each an IEEE operation per half), the same rounding
+// per element.  At 10 local steps the round runs ~70 fp32 ops per element:
+// unpacked that is ~60 % of the HBM time in VALU issue.
 typedef float f2 __attribute__((ext_vector_type(2)));
-template <bool MOM, int TERMS = 2>
-__device__ __forceinline__ void admm_ls_lane2(f2& w, f2& b, f2& a, f2 t, f2 th, float rho, float neg_lr, float mom,
-                                              int steps, bool first, double& rw, double& ra) {
-  const f2 rho2 = {rho, rho}, nlr2 = {neg_lr, neg_lr}, mom2 = {mom, mom};
+template <typename F> __device__ __forceinline__ F splat(float s) {
+  if constexpr (std::is_same<F, float>::value) return s;
+  else return F{s, s};
+}
+// the product of two floats is exact in double, so fma == the reference's
+// separately rounded r + v*v, one instruction fewer
+__device__ __forceinline__ void sq_acc(float v, double& r) { r = __builtin_fma(double(v), double(v), r); }
+__device__ __forceinline__ void sq_acc(f2 v, double& r) {
+  sq_acc(v.x, r);
+  sq_acc(v.y, r);
+}
+// an f4 column runs as two packed halves (v.xy, v.zw); join() repacks them
+__device__ __forceinline__ f4 join(f2 lo, f2 hi) { return f4{lo.x, lo.y, hi.x, hi.y}; }
+
+template <bool MOM, int TERMS, typename F>
+__device__ __forceinline__ void fed_ls_lane(F& w, F& b, F& a, F t, F th, float rho, float neg_lr, float mom, int steps,
+                                            bool first, double& rw, double& ra) {
+  const F rho_ = splat<F>(rho), nlr = splat<F>(neg_lr), mu = splat<F>(mom);
   w = th;
   for (int k = 0; k < steps; ++k) {
-    const f2 g = w - t;
-    f2 gg = g;
-    if constexpr (TERMS == 2) gg = g + (a + rho2 * (w - th));
-    if constexpr (TERMS == 1) gg = g + rho2 * (w - th);
-    f2 d = gg;
+    const F g = w - t;
+    F gg = g;
+    if constexpr (TERMS == 2) gg = g + (a + rho_ * (w - th));
+    if constexpr (TERMS == 1) gg = g + rho_ * (w - th);
+    F d = gg;
     if constexpr (MOM) {
-      b = (first && k == 0) ? gg : b * mom2 + gg;
+      b = (first && k == 0) ? gg : b * mu + gg;
       d = b;
     }
-    w = __builtin_elementwise_fma(nlr2, d, w);
+    w = __builtin_elementwise_fma(nlr, d, w);
   }
-  const f2 dl = w - th;
-  if constexpr (TERMS == 2) a = a + rho2 * dl;
-  rw = __builtin_fma(double(dl.x), double(dl.x), rw);
-  rw = __builtin_fma(double(dl.y), double(dl.y), rw);
-  if constexpr (TERMS == 2) {
-    ra = __builtin_fma(double(a.x), double(a.x), ra);
-    ra = __builtin_fma(double(a.y), double(a.y), ra);
-  }
+  const F dl = w - th;
+  if constexpr (TERMS == 2) a = a + rho_ * dl;
+  sq_acc(dl, rw);
+  if constexpr (TERMS == 2) sq_acc(a, ra);
 }
-// f4 = two packed halves
-template <bool MOM, int TERMS = 2>
-__device__ __forceinline__ void admm_ls_lane4(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
-                                              int steps, bool first, double& rw, double& ra) {
+template <bool MOM, int TERMS>
+__device__ __forceinline__ void fed_ls_lane(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
+                                            int steps, bool first, double& rw, double& ra) {
   f2 w0, w1, b0 = b.xy, b1 = b.zw, a0 = a.xy, a1 = a.zw;
-  admm_ls_lane2<MOM, TERMS>(w0, b0, a0, t.xy, th.xy, rho, neg_lr, mom, steps, first, rw, ra);
-  admm_ls_lane2<MOM, TERMS>(w1, b1, a1, t.zw, th.zw, rho, neg_lr, mom, steps, first, rw, ra);
-  w = f4{w0.x, w0.y, w1.x, w1.y};
-  b = f4{b0.x, b0.y, b1.x, b1.y};
-  a = f4{a0.x, a0.y, a1.x, a1.y};
+  fed_ls_lane<MOM, TERMS>(w0, b0, a0, f2(t.xy), f2(th.xy), rho, neg_lr, mom, steps, first, rw, ra);
+  fed_ls_lane<MOM, TERMS>(w1, b1, a1, f2(t.zw), f2(th.zw), rho, neg_lr, mom, steps, first, rw, ra);
+  w = join(w0, w1);
+  b = join(b0, b1);
+  a = join(a0, a1);
 }
 
 // TERMS < 2 (FedAvg / FedProx): A is NULL, no dual row is read or written and
@@ -307,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
   auto one = [&](int64_t c) {
     float w, b = MOM ? br[c] : 0.0f, a = 0.0f;
     if constexpr (DUAL) a = ar[c];
-    admm_ls_lane<MOM, TERMS>(w, b, a, tr[c], theta[c], rho, neg_lr, mom, steps, fst, rw, ra);
+    fed_ls_lane<MOM, TERMS>(w, b, a, tr[c], theta[c], rho, neg_lr, mom, steps, fst, rw, ra);
     wr[c] = w;
     if constexpr (DUAL) ar[c] = a;
     if constexpr (MOM) br[c] = b;
@@ -324,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void admm_ls_round_kernel(
         if constexpr (DUAL) a = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ar) + c);
         f4 b = MOM ? __builtin_nontemporal_load(reinterpret_cast<const f4*>(br) + c) : f4{0.f, 0.f, 0.f, 0.f};
         f4 w;
-        admm_ls_lane4<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, fst, rw, ra);
+        fed_ls_lane<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, fst, rw, ra);
         __builtin_nontemporal_store(w, reinterpret_cast<f4*>(wr) + c);
         if constexpr (DUAL) __builtin_nontemporal_store(a, reinterpret_cast<f4*>(ar) + c);
         if constexpr (MOM) __builtin_nontemporal_store(b, reinterpret_cast<f4*>(br) + c);
@@ -395,7 +392,7 @@ __global__ __launch_bounds__(kThreads) void ordered_sum_kernel(
 // DEC/servers.py:50-81 on least squares: every sampled client's
 // update_weights, DEC/clients.py:36-53, then average_weights, :42-48).
 // Column-strip major: each lane owns one V-column and walks the m sampled
-// agents in the given order, running admm_ls_lane on (agent, column) and
+// agents in the given order, running fed_ls_lane on (agent, column) and
 // chaining acc = w(first) ; acc = fl(acc + w) — the ordered_sum_kernel's
 // association, so theta_next is the same bits as admm_ls_round_kernel +
 // ordered_sum_kernel — while the w rows are still in registers: the separate
@@ -409,18 +406,6 @@ __global__ __launch_bounds__(kThreads) void ordered_sum_kernel(
 // ----------------------------------------------------------------------------
 constexpr int kRoundPF = 3;
 
-template <bool MOM, int TERMS>
-__device__ __forceinline__ void admm_ls_lane_v(float& w, float& b, float& a, float t, float th, float rho, float neg_lr,
-                                               float mom, int steps, bool first, double& rw, double& ra) {
-  admm_ls_lane<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
-}
-// packed (measured at 8192 x 2^20, 10 steps: 34.6-35.1 ms vs 36.0-36.5 with
-// the per-element scalar form, profiles/r05zw_admm_round_ab.jsonl)
-template <bool MOM, int TERMS>
-__device__ __forceinline__ void admm_ls_lane_v(f4& w, f4& b, f4& a, f4 t, f4 th, float rho, float neg_lr, float mom,
-                                               int steps, bool first, double& rw, double& ra) {
-  admm_ls_lane4<MOM, TERMS>(w, b, a, t, th, rho, neg_lr, mom, steps, first, rw, ra);
-}
 __device__ __forceinline__ float ldnt(const float* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ f4 ldnt(const f4* p) { return __builtin_nontemporal_load(p); }
 // nontemporal buffer store of lane value v at byte offset voff of the row at
@@ -432,20 +417,6 @@ __device__ __forceinline__ void st_row(float v, float* base, int64_t nbytes, uin
 __device__ __forceinline__ void st_row(f4 v, float* base, int64_t nbytes, uint32_t voff) {
   const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, static_cast<int>(nbytes), 0x00020000);
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), rs, voff, 0, 2);
-}
-
-template <int NT>
-__device__ __forceinline__ double block_sum_f64_nt(double v, double* smem) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) smem[wid] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-    for (int i = 0; i < NT / 64; ++i) s += smem[i];
-  }
-  return s;
 }
 
 // One prefetch group of the one-pass round: PF agents' target, dual and
@@ -508,7 +479,7 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
     V w, bu = MOM ? g.b[u] : vzero(th), au = vzero(th);
     if constexpr (DUAL) au = g.a[u];
     double rwu = 0.0, rau = 0.0;
-    admm_ls_lane_v<MOM, TERMS>(w, bu, au, g.t[u], th, rho, neg_lr, mom, steps, fst, rwu, rau);
+    fed_ls_lane<MOM, TERMS>(w, bu, au, g.t[u], th, rho, neg_lr, mom, steps, fst, rwu, rau);
     st(w, W, ldw, g.row[u]);
     if constexpr (DUAL) st(au, A, lda, g.row[u]);
     if constexpr (MOM) st(bu, B, ldb, g.row[u]);
@@ -535,11 +506,11 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
     *(reinterpret_cast<V*>(out + c_off) + c) = acc;
   }
   if constexpr (RESID) {
-    const double sw = block_sum_f64_nt<NT>(rw, smem);
+    const double sw = block_sum_f64<NT>(rw, smem);
     double sa = 0.0;
     if constexpr (DUAL) {
       __syncthreads();
-      sa = block_sum_f64_nt<NT>(ra, smem);
+      sa = block_sum_f64<NT>(ra, smem);
     }
     if (threadIdx.x == 0) {
       partial[part_off + blockIdx.x] = sw;
@@ -556,7 +527,7 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
 // template's instantiations moves).  Per sampled agent k (row a) and column:
 //   w = theta
 //   local_steps times:  g = fl(w - t_a);  g' = fl(fl(g + c) - c_a)       (:155)
-//     momentum SGD as admm_ls_lane
+//     momentum SGD as fed_ls_lane
 //   dl   = fl(w - theta)                                                  (:162)
 //   c_a' = fl(fl(c_a - c) - fl(dl * inv))   inv = 1 / (local_steps * lr)  (:165)
 //   dc   = fl(c_a' - c_a)                                                 (:167)
@@ -568,16 +539,6 @@ __global__ __launch_bounds__(NT) void admm_ls_round_mean_kernel(
 // per lane like theta.  RESID: (dl^2, c_a'^2) summed as the FedADMM round's.
 // F is float or f2 (packed, an IEEE operation per half).
 // ----------------------------------------------------------------------------
-template <typename F> __device__ __forceinline__ F splat(float s) {
-  if constexpr (std::is_same<F, float>::value) return s;
-  else return F{s, s};
-}
-__device__ __forceinline__ void sq_acc(float v, double& r) { r = __builtin_fma(double(v), double(v), r); }
-__device__ __forceinline__ void sq_acc(f2 v, double& r) {
-  sq_acc(v.x, r);
-  sq_acc(v.y, r);
-}
-
 template <bool MOM, typename F>
 __device__ __forceinline__ void scaffold_ls_lane(F& w, F& b, F& ca, F& dl, F& dc, F t, F th, F c, float neg_lr,
                                                  float mom, float inv, int steps, bool first, double& rw, double& ra) {
@@ -600,25 +561,18 @@ __device__ __forceinline__ void scaffold_ls_lane(F& w, F& b, F& ca, F& dl, F& dc
   sq_acc(dl, rw);
   sq_acc(cn, ra);
 }
-template <bool MOM>
-__device__ __forceinline__ void scaffold_ls_lane_v(float& w, float& b, float& ca, float& dl, float& dc, float t,
-                                                   float th, float c, float neg_lr, float mom, float inv, int steps,
-                                                   bool first, double& rw, double& ra) {
-  scaffold_ls_lane<MOM, float>(w, b, ca, dl, dc, t, th, c, neg_lr, mom, inv, steps, first, rw, ra);
-}
 // f4 = two packed halves
 template <bool MOM>
-__device__ __forceinline__ void scaffold_ls_lane_v(f4& w, f4& b, f4& ca, f4& dl, f4& dc, f4 t, f4 th, f4 c,
-                                                   float neg_lr, float mom, float inv, int steps, bool first,
-                                                   double& rw, double& ra) {
+__device__ __forceinline__ void scaffold_ls_lane(f4& w, f4& b, f4& ca, f4& dl, f4& dc, f4 t, f4 th, f4 c, float neg_lr,
+                                                 float mom, float inv, int steps, bool first, double& rw, double& ra) {
   f2 w0, w1, b0 = b.xy, b1 = b.zw, a0 = ca.xy, a1 = ca.zw, l0, l1, d0, d1;
-  scaffold_ls_lane<MOM, f2>(w0, b0, a0, l0, d0, t.xy, th.xy, c.xy, neg_lr, mom, inv, steps, first, rw, ra);
-  scaffold_ls_lane<MOM, f2>(w1, b1, a1, l1, d1, t.zw, th.zw, c.zw, neg_lr, mom, inv, steps, first, rw, ra);
-  w = f4{w0.x, w0.y, w1.x, w1.y};
-  b = f4{b0.x, b0.y, b1.x, b1.y};
-  ca = f4{a0.x, a0.y, a1.x, a1.y};
-  dl = f4{l0.x, l0.y, l1.x, l1.y};
-  dc = f4{d0.x, d0.y, d1.x, d1.y};
+  scaffold_ls_lane<MOM>(w0, b0, a0, l0, d0, f2(t.xy), f2(th.xy), f2(c.xy), neg_lr, mom, inv, steps, first, rw, ra);
+  scaffold_ls_lane<MOM>(w1, b1, a1, l1, d1, f2(t.zw), f2(th.zw), f2(c.zw), neg_lr, mom, inv, steps, first, rw, ra);
+  w = join(w0, w1);
+  b = join(b0, b1);
+  ca = join(a0, a1);
+  dl = join(l0, l1);
+  dc = join(d0, d1);
 }
 __device__ __forceinline__ float vscale(float a, float s) { return a * s; }
 __device__ __forceinline__ f4 vscale(f4 a, float s) { return f4{a.x * s, a.y * s, a.z * s, a.w * s}; }
@@ -667,7 +621,7 @@ __global__ __launch_bounds__(NT) void scaffold_ls_round_kernel(
     const bool fst = first ? first[k] != 0 : false;
     V w, dl, dc, bu = MOM ? g.b[u] : vzero(th), au = g.a[u];
     double rwu = 0.0, rau = 0.0;
-    scaffold_ls_lane_v<MOM>(w, bu, au, dl, dc, g.t[u], th, cg, neg_lr, mom, inv, steps, fst, rwu, rau);
+    scaffold_ls_lane<MOM>(w, bu, au, dl, dc, g.t[u], th, cg, neg_lr, mom, inv, steps, fst, rwu, rau);
     st(w, W, ldw, g.row[u]);
     st(au, CI, ldc, g.row[u]);
     if constexpr (MOM) st(bu, B, ldb, g.row[u]);
@@ -695,14 +649,72 @@ __global__ __launch_bounds__(NT) void scaffold_ls_round_kernel(
     *(reinterpret_cast<V*>(c_out + c_off) + c) = vadd(cg, vdiv(acc_c, scale_c));
   }
   if constexpr (RESID) {
-    const double sw = block_sum_f64_nt<NT>(rw, smem);
+    const double sw = block_sum_f64<NT>(rw, smem);
     __syncthreads();
-    const double sa = block_sum_f64_nt<NT>(ra, smem);
+    const double sa = block_sum_f64<NT>(ra, smem);
     if (threadIdx.x == 0) {
       partial[part_off + blockIdx.x] = sw;
       partial[part_stride + part_off + blockIdx.x] = sa;
     }
   }
+}
+
+// Chunks per row of the per-row kernels (admm_dual_kernel, admm_ls_round_kernel:
+// kThreads x kDualIters V-columns a block); 0: too many blocks for one launch.
+int64_t row_chunks(int64_t P, bool vec, int64_t rows) {
+  const int64_t per_block = int64_t(kThreads) * kDualIters;
+  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
+  return mul_sat(chunks, rows) > kMaxBlocks ? 0 : chunks;
+}
+
+// The argument rules the one-pass rounds share, after each round's own.
+// m_why: why there must be a first sampled client; ld_short: some row matrix
+// in use has ld < P.
+int check_strip_round(const char* nm, int32_t m, const char* m_why, int64_t P, bool ld_short,
+                      const double* resid_total, const void* work) {
+  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (%s)", nm, m_why);
+  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
+  if (ld_short) return fail(DOL_EINVAL, "%s: ld < P", nm);
+  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  return DOL_OK;
+}
+
+// One launch of a one-pass round: `blocks` strips of nt lanes over the ncols
+// V-columns at c_off, their residual partials at part_off of [2][part_stride].
+struct Strip {
+  int nt;
+  int64_t c_off, ncols, blocks;
+  double* partial;
+  int64_t part_off, part_stride;
+};
+
+// The launch plan of the one-pass rounds: columns [0, n4) as f4 where every
+// (pointer, ld) of `rows` allows it, the rest scalar, one launch(V{}, Strip)
+// each, then the fixed-order fold of the block partials into the n_totals
+// doubles of resid_total (if asked for).
+template <typename Launch>
+void launch_strips(int64_t P, std::initializer_list<std::pair<const void*, int64_t>> rows, double* resid_total,
+                   int n_totals, void* work, hipStream_t s, Launch launch) {
+  bool vec_ok = true;
+  for (const auto& r : rows) vec_ok = vec_ok && row_vec_ok(r.first, r.second);
+  const ColSplit cs = split_cols(P, vec_ok);
+  // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
+  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
+  // lanes per CU) take 256-lane strips: the strips are the only parallelism
+  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
+  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
+  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
+  // for the two-kernel round (row-major client round + ordered sum), which
+  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
+  const int n_cu = n_cus() > 0 ? n_cus() : 256;
+  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
+  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
+  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
+  const int64_t nb = nb4 + nbt;
+  double* partial = static_cast<double*>(work);
+  if (cs.n4 > 0) launch(f4{}, Strip{nt, 0, cs.n4, nb4, partial, 0, nb});
+  if (cs.tail > 0) launch(float{}, Strip{nt, cs.n4 * 4, cs.tail, nbt, partial, nb4, nb});
+  if (resid_total) hipLaunchKernelGGL(resid_reduce_kernel, dim3(n_totals), dim3(kThreads), 0, s, partial, nb, resid_total);
 }
 
 // The least-squares client round of the three algorithms; nm names the entry
@@ -732,9 +744,8 @@ int fed_ls_round(const char* nm, float* w, int64_t ldw, float* buf, int64_t ldb,
   }
   const bool vec = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
                    (!mom || row_vec_ok(buf, ldb));
-  const int64_t per_block = int64_t(kThreads) * kDualIters;
-  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
-  if (mul_sat(chunks, m) > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large", nm);
+  const int64_t chunks = row_chunks(P, vec, m);
+  if (!chunks) return fail(DOL_EINVAL, "%s: problem too large", nm);
   double* partial = static_cast<double*>(work);
   const dim3 grid(static_cast<unsigned>(chunks * m));
   dispatch([&](auto vc, auto mc, auto rc, auto tc) {
@@ -763,7 +774,6 @@ int fed_ls_round_mean(const char* nm, float* w, int64_t ldw, float* buf, int64_t
     lda = 0;
   }
   DOL_DIMS_OK(nm, ldw, ldb, lda, ldt, P);
-  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the average indexes w[0])", nm);
   if (P < 0 || local_steps < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
   if (!(scale > 0.0f)) return fail(DOL_EINVAL, "%s: scale must be > 0", nm);
   const bool mom = momentum != 0.0f;
@@ -771,47 +781,25 @@ int fed_ls_round_mean(const char* nm, float* w, int64_t ldw, float* buf, int64_t
     return fail(DOL_EINVAL, "%s: null pointer", nm);
   if (theta_out == w || (dual && theta_out == alpha) || theta_out == target || (mom && theta_out == buf))
     return fail(DOL_EINVAL, "%s: theta_out aliases the rows", nm);
-  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
-  if (ldw < P || (dual && lda < P) || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
-  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  DOL_CHECKED(check_strip_round(nm, m, "the average indexes w[0]", P,
+                                ldw < P || (dual && lda < P) || ldt < P || (mom && ldb < P), resid_total, work));
   if (P == 0) {
     if (resid_total) (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
     return check_launch(nm);
   }
-  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(alpha, lda) && row_vec_ok(target, ldt) &&
-                      row_vec_ok(theta, 0) && row_vec_ok(theta_out, 0) && (!mom || row_vec_ok(buf, ldb));
-  const ColSplit cs = split_cols(P, vec_ok);
-  // column strip per workgroup: 1024 lanes (16 KiB of each row per workgroup,
-  // one workgroup per CU at 2^20 columns).  Narrower blocks (fewer than 1024
-  // lanes per CU) take 256-lane strips: the strips are the only parallelism
-  // (the sum over agents is sequential per column).  At 8192 x 2^17 (a
-  // column-sharded rank's block at 8 ranks): 18.6 ms with 1024-lane strips,
-  // 7.4 with 256, 7.65 with one-wave strips and 8 agents in flight -- and 5.15
-  // for the two-kernel round (row-major client round + ordered sum), which
-  // SeparableADMM(shard="columns") takes there (profiles/r06c_admm_narrow_ab.jsonl).
-  const int n_cu = n_cus() > 0 ? n_cus() : 256;
-  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
-  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
-  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
-  const int64_t nb = nb4 + nbt;
-  double* partial = static_cast<double*>(work);
   const int do_div = scale != 1.0f;
-  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
+  launch_strips(P, {{w, ldw}, {alpha, lda}, {target, ldt}, {theta, 0}, {theta_out, 0}, {mom ? buf : nullptr, ldb}},
+                resid_total, dual ? 2 : 1, work, s, [&](auto vt, const Strip& st) {
     dispatch([&](auto mc, auto rc, auto ntc, auto tc) {
       hipLaunchKernelGGL((admm_ls_round_mean_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
                                                     decltype(ntc)::value, decltype(tc)::value>),
-                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, alpha, lda, target, ldt,
-                         theta, agents, first, m, c_off, ncols, rho, -lr, momentum, local_steps, theta_out, scale, do_div,
-                         partial, part_off, nb);
-    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt}, Ints<0, 1, 2>{alg});
-  };
-  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
-  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
-  if (resid_total) {
-    // FedAvg / FedProx: no ||alpha||^2 partials were written; the second total is 0
-    hipLaunchKernelGGL(resid_reduce_kernel, dim3(dual ? 2 : 1), dim3(kThreads), 0, s, partial, nb, resid_total);
-    if (!dual) (void)hipMemsetAsync(resid_total + 1, 0, sizeof(double), s);
-  }
+                         dim3(static_cast<unsigned>(st.blocks)), dim3(st.nt), 0, s, w, ldw, buf, ldb, alpha, lda, target,
+                         ldt, theta, agents, first, m, st.c_off, st.ncols, rho, -lr, momentum, local_steps, theta_out,
+                         scale, do_div, st.partial, st.part_off, st.part_stride);
+    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{st.nt}, Ints<0, 1, 2>{alg});
+  });
+  // FedAvg / FedProx: no ||alpha||^2 partials were written; the second total is 0
+  if (resid_total && !dual) (void)hipMemsetAsync(resid_total + 1, 0, sizeof(double), s);
   return check_launch(nm);
 }
 
@@ -922,9 +910,8 @@ int dol_admm_dual_f32(float* alpha, int64_t lda, const float* w, int64_t ldw, co
     return check_launch("dol_admm_dual_f32");
   }
   const bool vec = row_vec_ok(alpha, lda) && row_vec_ok(w, ldw) && row_vec_ok(theta, 0);
-  const int64_t per_block = int64_t(kThreads) * kDualIters;
-  const int64_t chunks = vec ? std::max<int64_t>(1, cdiv(P / 4, per_block)) : cdiv(P, per_block);
-  if (mul_sat(chunks, n_agents) > kMaxBlocks) return fail(DOL_EINVAL, "dol_admm_dual_f32: problem too large");
+  const int64_t chunks = row_chunks(P, vec, n_agents);
+  if (!chunks) return fail(DOL_EINVAL, "dol_admm_dual_f32: problem too large");
   double* partial = static_cast<double*>(work);
   const dim3 grid(static_cast<unsigned>(chunks * n_agents));
   dispatch([&](auto vc, auto rc) {
@@ -990,7 +977,6 @@ int dol_scaffold_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, fl
                               void* work, hipStream_t s) {
   const char* nm = "dol_scaffold_ls_round_f32";
   DOL_DIMS_OK(nm, ldw, ldb, ldc, ldt, P);
-  if (m < 1) return fail(DOL_EINVAL, "%s: m must be >= 1 (the chains start at the first sampled client)", nm);
   if (P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
   if (local_steps < 1) return fail(DOL_EINVAL, "%s: local_steps must be >= 1", nm);
   if (!(scale_w > 0.0f) || !(scale_c > 0.0f)) return fail(DOL_EINVAL, "%s: scale_w and scale_c must be > 0", nm);
@@ -1001,37 +987,24 @@ int dol_scaffold_ls_round_f32(float* w, int64_t ldw, float* buf, int64_t ldb, fl
     if (out && (out == w || out == ci || out == target || (mom && out == buf)))
       return fail(DOL_EINVAL, "%s: %s aliases the rows", nm, out == theta_out ? "theta_out" : "c_out");
   if (theta_out && theta_out == c_out) return fail(DOL_EINVAL, "%s: theta_out and c_out alias", nm);
-  if (resid_total && !work && P > 0) return fail(DOL_EINVAL, "%s: resid_total needs a workspace", nm);
-  if (ldw < P || ldc < P || ldt < P || (mom && ldb < P)) return fail(DOL_EINVAL, "%s: ld < P", nm);
-  if (P > (int64_t(1) << 29) - 16) return fail(DOL_EINVAL, "%s: P >= 2^29 (row offsets are 32-bit buffer offsets)", nm);
+  DOL_CHECKED(check_strip_round(nm, m, "the chains start at the first sampled client", P,
+                                ldw < P || ldc < P || ldt < P || (mom && ldb < P), resid_total, work));
   if (P == 0) {  // nothing to do but to zero the totals
     if (!resid_total) { g_err[0] = '\0'; return DOL_OK; }
     (void)hipMemsetAsync(resid_total, 0, 2 * sizeof(double), s);
     return check_launch(nm);
   }
-  const bool vec_ok = row_vec_ok(w, ldw) && row_vec_ok(ci, ldc) && row_vec_ok(target, ldt) && row_vec_ok(theta, 0) &&
-                      row_vec_ok(c, 0) && row_vec_ok(theta_out, 0) && row_vec_ok(c_out, 0) &&
-                      (!mom || row_vec_ok(buf, ldb));
-  const ColSplit cs = split_cols(P, vec_ok);
-  // the strip choice of fed_ls_round_mean: 1024 lanes at one workgroup per CU and up, else 256
-  const int n_cu = n_cus() > 0 ? n_cus() : 256;
-  const int64_t lanes = std::max<int64_t>(cs.n4, cs.tail);
-  const int nt = lanes >= int64_t(1024) * n_cu ? 1024 : 256;
-  const int64_t nb4 = cdiv(cs.n4, nt), nbt = cdiv(cs.tail, nt);
-  const int64_t nb = nb4 + nbt;
-  double* partial = static_cast<double*>(work);
-  auto both = [&](auto vt, int64_t c_off, int64_t ncols, int64_t blocks, int64_t part_off) {
+  launch_strips(P, {{w, ldw}, {ci, ldc}, {target, ldt}, {theta, 0}, {c, 0}, {theta_out, 0}, {c_out, 0},
+                    {mom ? buf : nullptr, ldb}},
+                resid_total, 2, work, s, [&](auto vt, const Strip& st) {
     dispatch([&](auto mc, auto rc, auto ntc) {
       hipLaunchKernelGGL((scaffold_ls_round_kernel<decltype(vt), decltype(mc)::value, decltype(rc)::value,
                                                    decltype(ntc)::value>),
-                         dim3(static_cast<unsigned>(blocks)), dim3(nt), 0, s, w, ldw, buf, ldb, ci, ldc, target, ldt,
-                         theta, c, agents, first, m, c_off, ncols, -lr, momentum, local_steps, inv_steps_lr, global_lr,
-                         theta_out, scale_w, c_out, scale_c, partial, part_off, nb);
-    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{nt});
-  };
-  if (cs.n4 > 0) both(f4{}, 0, cs.n4, nb4, 0);
-  if (cs.tail > 0) both(float{}, cs.n4 * 4, cs.tail, nbt, nb4);
-  if (resid_total) hipLaunchKernelGGL(resid_reduce_kernel, dim3(2), dim3(kThreads), 0, s, partial, nb, resid_total);
+                         dim3(static_cast<unsigned>(st.blocks)), dim3(st.nt), 0, s, w, ldw, buf, ldb, ci, ldc, target, ldt,
+                         theta, c, agents, first, m, st.c_off, st.ncols, -lr, momentum, local_steps, inv_steps_lr,
+                         global_lr, theta_out, scale_w, c_out, scale_c, st.partial, st.part_off, st.part_stride);
+    }, Bool{mom}, Bool{resid_total != nullptr}, Ints<1024, 256>{st.nt});
+  });
   return check_launch(nm);
 }
 

@@ -22,7 +22,6 @@ from typing import Optional
 
 import torch
 
-from . import _native
 from . import ops as _ops
 
 
@@ -54,25 +53,10 @@ def fed_ls_round(w: torch.Tensor, alpha: Optional[torch.Tensor], target: torch.T
     Reference: DEC/clients.py:36-53 with update_model :85-95 / :101-115 /
     :125-139 and update_duals :58-59 / :141-144."""
     alg = _algorithm("fed_ls_round", algorithm, alpha)
-    duals = alg == 2
-    if not duals and alpha_sq is not None:
+    if alg != 2 and alpha_sq is not None:
         raise ValueError(f"fed_ls_round: '{algorithm}' has no duals (alpha_sq must be None)")
-    P, n, ldw, lda, ldt, ldb = _ops._ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P,
-                                                   duals=duals)
-    m = n if agents is None else agents.numel()
-    if first is not None:
-        _ops._check_array("first", first, torch.int32, m, w.device)
-    if duals and (resid_sq is None) != (alpha_sq is None):
-        raise ValueError("pass both resid_sq and alpha_sq or neither")
-    if resid_sq is not None:
-        _ops._check_array("resid_sq", resid_sq, torch.float64, m, w.device)
-        if duals:
-            _ops._check_array("alpha_sq", alpha_sq, torch.float64, m, w.device)
-        work = _ops._workspace(work, _ops.admm_ls_round_workspace_bytes(m, P), w.device)
-    _native.call("dol_fed_ls_round_f32", w.data_ptr(), ldw, _ops._ptr(buf) if ldb else None, ldb, _ops._ptr(alpha),
-                 lda, target.data_ptr(), ldt, theta.data_ptr(), _ops._ptr(agents), _ops._ptr(first), m, P, alg,
-                 float(rho), float(lr), float(momentum), int(local_steps), _ops._ptr(resid_sq), _ops._ptr(alpha_sq),
-                 _ops._ptr(work) if resid_sq is not None else None, _ops._stream(w))
+    _ops._ls_round("dol_fed_ls_round_f32", alg, w, alpha, target, theta, agents, first, buf, rho, lr, momentum,
+                   local_steps, resid_sq, alpha_sq, work, P)
 
 
 def fed_ls_round_mean(w: torch.Tensor, alpha: Optional[torch.Tensor], target: torch.Tensor, theta: torch.Tensor,
@@ -90,20 +74,5 @@ def fed_ls_round_mean(w: torch.Tensor, alpha: Optional[torch.Tensor], target: to
     validate (default): the host check that `agents` are distinct rows of w;
     it is not made while the stream is being captured into a graph."""
     alg = _algorithm("fed_ls_round_mean", algorithm, alpha)
-    P, n, ldw, lda, ldt, ldb = _ops._ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P,
-                                                   duals=alg == 2)
-    m = _ops._check_distinct_agents("fed_ls_round_mean", agents, n, validate)
-    if first is not None:
-        _ops._check_array("first", first, torch.int32, m, w.device)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=w.device)
-    _ops._check_vec("out", out, P, w.device)
-    if resid_total is not None:
-        _ops._check_array("resid_total", resid_total, torch.float64, 2, w.device)
-        work = _ops._workspace(work, int(_native.lib().dol_admm_ls_round_mean_workspace_bytes(int(P))), w.device)
-    _native.call("dol_fed_ls_round_mean_f32", w.data_ptr(), ldw, _ops._ptr(buf) if ldb else None, ldb,
-                 _ops._ptr(alpha), lda, target.data_ptr(), ldt, theta.data_ptr(), _ops._ptr(agents), _ops._ptr(first),
-                 m, P, alg, float(rho), float(lr), float(momentum), int(local_steps), out.data_ptr(),
-                 float(m if scale is None else scale), _ops._ptr(resid_total),
-                 _ops._ptr(work) if resid_total is not None else None, _ops._stream(w))
-    return out
+    return _ops._ls_round_mean("fed_ls_round_mean", "dol_fed_ls_round_mean_f32", alg, w, alpha, target, theta, agents,
+                               first, buf, rho, lr, momentum, local_steps, out, scale, resid_total, work, P, validate)

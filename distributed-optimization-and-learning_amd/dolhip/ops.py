@@ -888,6 +888,60 @@ def _check_distinct_agents(name: str, agents: Optional[torch.Tensor], n: int, va
     return m
 
 
+def _one_pass_outputs(w: torch.Tensor, m: int, P: int, first: Optional[torch.Tensor], outs, resid_total, work):
+    """What the one-pass wrappers (round + mean, SCAFFOLD) share after their
+    row checks: `first` is int32 [m]; each (name, vector) of `outs` is a float32
+    [P] device vector, a fresh one where None; resid_total is float64 [2] and
+    brings the workspace with it.  Returns (the output vectors, work)."""
+    if first is not None:
+        _check_array("first", first, torch.int32, m, w.device)
+    vecs = [torch.empty(P, dtype=torch.float32, device=w.device) if t is None else t for _, t in outs]
+    for (name, _), t in zip(outs, vecs):
+        _check_vec(name, t, P, w.device)
+    if resid_total is not None:
+        _check_array("resid_total", resid_total, torch.float64, 2, w.device)
+        work = _workspace(work, int(_native.lib().dol_admm_ls_round_mean_workspace_bytes(int(P))), w.device)
+    return vecs, work
+
+
+def _ls_round(entry: str, alg: Optional[int], w, alpha, target, theta, agents, first, buf, rho, lr, momentum,
+              local_steps, resid_sq, alpha_sq, work, P) -> None:
+    """The body of admm_ls_round (alg None: `entry` takes no algorithm) and of
+    fed_ls.fed_ls_round (alg = DOL_FED_*, passed on to `entry`)."""
+    duals = alg is None or alg == 2
+    P, n, ldw, lda, ldt, ldb = _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P,
+                                              duals=duals)
+    m = n if agents is None else agents.numel()
+    if first is not None:
+        _check_array("first", first, torch.int32, m, w.device)
+    if duals and (resid_sq is None) != (alpha_sq is None):
+        raise ValueError("pass both resid_sq and alpha_sq or neither")
+    if resid_sq is not None:
+        _check_array("resid_sq", resid_sq, torch.float64, m, w.device)
+        if duals:
+            _check_array("alpha_sq", alpha_sq, torch.float64, m, w.device)
+        work = _workspace(work, admm_ls_round_workspace_bytes(m, P), w.device)
+    _native.call(entry, w.data_ptr(), ldw, _ptr(buf) if ldb else None, ldb, _ptr(alpha), lda, target.data_ptr(), ldt,
+                 theta.data_ptr(), _ptr(agents), _ptr(first), m, P, *(() if alg is None else (alg,)), float(rho),
+                 float(lr), float(momentum), int(local_steps), _ptr(resid_sq), _ptr(alpha_sq),
+                 _ptr(work) if resid_sq is not None else None, _stream(w))
+
+
+def _ls_round_mean(name: str, entry: str, alg: Optional[int], w, alpha, target, theta, agents, first, buf, rho, lr,
+                   momentum, local_steps, out, scale, resid_total, work, P, validate) -> torch.Tensor:
+    """The body of admm_ls_round_mean and of fed_ls.fed_ls_round_mean; `name`
+    is the wrapper's, for the messages, and alg as in _ls_round."""
+    P, n, ldw, lda, ldt, ldb = _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P,
+                                              duals=alg is None or alg == 2)
+    m = _check_distinct_agents(name, agents, n, validate)
+    (out,), work = _one_pass_outputs(w, m, P, first, (("out", out),), resid_total, work)
+    _native.call(entry, w.data_ptr(), ldw, _ptr(buf) if ldb else None, ldb, _ptr(alpha), lda, target.data_ptr(), ldt,
+                 theta.data_ptr(), _ptr(agents), _ptr(first), m, P, *(() if alg is None else (alg,)), float(rho),
+                 float(lr), float(momentum), int(local_steps), out.data_ptr(), float(m if scale is None else scale),
+                 _ptr(resid_total), _ptr(work) if resid_total is not None else None, _stream(w))
+    return out
+
+
 def admm_ls_round(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, theta: torch.Tensor,
                   agents: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
                   buf: Optional[torch.Tensor] = None, rho: float = 0.1, lr: float = 0.1, momentum: float = 0.0,
@@ -902,20 +956,8 @@ def admm_ls_round(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, th
     resid_sq / alpha_sq: float64 [m] outputs (||w - theta||^2, ||alpha||^2).
     Reference: DEC/clients.py:36-53, :125-144 (update_weights, update_model,
     update_duals) with the CNN loss replaced by least squares."""
-    P, n, ldw, lda, ldt, ldb = _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P)
-    m = n if agents is None else agents.numel()
-    if first is not None:
-        _check_array("first", first, torch.int32, m, w.device)
-    if (resid_sq is None) != (alpha_sq is None):
-        raise ValueError("pass both resid_sq and alpha_sq or neither")
-    if resid_sq is not None:
-        _check_array("resid_sq", resid_sq, torch.float64, m, w.device)
-        _check_array("alpha_sq", alpha_sq, torch.float64, m, w.device)
-        work = _workspace(work, admm_ls_round_workspace_bytes(m, P), w.device)
-    _native.call("dol_admm_ls_round_f32", w.data_ptr(), ldw, _ptr(buf) if ldb else None, ldb, alpha.data_ptr(), lda,
-                 target.data_ptr(), ldt, theta.data_ptr(), _ptr(agents), _ptr(first), m, P, float(rho), float(lr),
-                 float(momentum), int(local_steps), _ptr(resid_sq), _ptr(alpha_sq),
-                 _ptr(work) if resid_sq is not None else None, _stream(w))
+    _ls_round("dol_admm_ls_round_f32", None, w, alpha, target, theta, agents, first, buf, rho, lr, momentum,
+              local_steps, resid_sq, alpha_sq, work, P)
 
 
 def admm_ls_round_mean(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, theta: torch.Tensor,
@@ -939,21 +981,8 @@ def admm_ls_round_mean(w: torch.Tensor, alpha: torch.Tensor, target: torch.Tenso
     checked them (SeparableADMM.round) pass validate=False.  The check is not
     made while the stream is being captured into a graph.
     Reference: DEC/servers.py:50-81 (Server.run's round) on least squares."""
-    P, n, ldw, lda, ldt, ldb = _ls_round_args(w, alpha, target, theta, agents, buf, momentum, local_steps, P)
-    m = _check_distinct_agents("admm_ls_round_mean", agents, n, validate)
-    if first is not None:
-        _check_array("first", first, torch.int32, m, w.device)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=w.device)
-    _check_vec("out", out, P, w.device)
-    if resid_total is not None:
-        _check_array("resid_total", resid_total, torch.float64, 2, w.device)
-        work = _workspace(work, int(_native.lib().dol_admm_ls_round_mean_workspace_bytes(int(P))), w.device)
-    _native.call("dol_admm_ls_round_mean_f32", w.data_ptr(), ldw, _ptr(buf) if ldb else None, ldb, alpha.data_ptr(),
-                 lda, target.data_ptr(), ldt, theta.data_ptr(), _ptr(agents), _ptr(first), m, P, float(rho), float(lr),
-                 float(momentum), int(local_steps), out.data_ptr(), float(m if scale is None else scale),
-                 _ptr(resid_total), _ptr(work) if resid_total is not None else None, _stream(w))
-    return out
+    return _ls_round_mean("admm_ls_round_mean", "dol_admm_ls_round_mean_f32", None, w, alpha, target, theta, agents,
+                          first, buf, rho, lr, momentum, local_steps, out, scale, resid_total, work, P, validate)
 
 
 # ---------------------------------------------------------------------------

@@ -62,14 +62,8 @@ def scaffold_ls_round(w: torch.Tensor, ci: torch.Tensor, target: torch.Tensor, t
     P, n, ldw, ldc, ldt, ldb = _ops._ls_round_args(w, ci, target, theta, agents, buf, momentum, local_steps, P)
     _ops._check_vec("c", c, P, w.device)
     m = _ops._check_distinct_agents("scaffold_ls_round", agents, n, validate)
-    if first is not None:
-        _ops._check_array("first", first, torch.int32, m, w.device)
-    if theta_out is None:
-        theta_out = torch.empty(P, dtype=torch.float32, device=w.device)
-    if c_out is None:
-        c_out = torch.empty(P, dtype=torch.float32, device=w.device)
-    _ops._check_vec("theta_out", theta_out, P, w.device)
-    _ops._check_vec("c_out", c_out, P, w.device)
+    (theta_out, c_out), work = _ops._one_pass_outputs(w, m, P, first, (("theta_out", theta_out), ("c_out", c_out)),
+                                                      resid_total, work)
     rows = [w, ci, target] + ([buf] if ldb else [])
     for name, out in (("theta_out", theta_out), ("c_out", c_out)):
         if any(out.data_ptr() == r.data_ptr() for r in rows):
@@ -80,9 +74,6 @@ def scaffold_ls_round(w: torch.Tensor, ci: torch.Tensor, target: torch.Tensor, t
     scale_w = float(m if scale_w is None else scale_w)
     if n_total < 1 or not scale_w > 0.0:
         raise ValueError("scaffold_ls_round: n_total must be >= 1 and scale_w > 0")
-    if resid_total is not None:
-        _ops._check_array("resid_total", resid_total, torch.float64, 2, w.device)
-        work = _ops._workspace(work, int(_native.lib().dol_admm_ls_round_mean_workspace_bytes(int(P))), w.device)
     _native.call("dol_scaffold_ls_round_f32", w.data_ptr(), ldw, _ops._ptr(buf) if ldb else None, ldb, ci.data_ptr(),
                  ldc, target.data_ptr(), ldt, theta.data_ptr(), c.data_ptr(), _ops._ptr(agents), _ops._ptr(first), m, P,
                  float(lr), float(momentum), int(local_steps), inv_steps_lr(local_steps, lr), float(global_lr),

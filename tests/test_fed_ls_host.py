@@ -338,6 +338,75 @@ def test_ops_alpha_sq_is_refused_without_duals(rec):
     assert rec.calls == []
 
 
+class _OnGpu(torch.Tensor):
+    """A host tensor that says it is on cuda:0, so that the wrappers' checks
+    past "no CPU path" run without a GPU; nothing is launched on it."""
+    device = property(lambda self: torch.device("cuda", 0))
+
+
+def _gpu(*shape, dtype=torch.float32):
+    return torch.zeros(*shape, dtype=dtype).as_subclass(_OnGpu)
+
+
+def _ids(*ids):
+    return torch.tensor(ids, dtype=torch.int32).as_subclass(_OnGpu)
+
+
+_F64 = torch.float64
+# the argument errors of the round (first block) and round + mean (second) wrappers: what to pass wrong
+ROUND_ERRORS = {
+    "first_dtype": dict(first=_gpu(4)),
+    "first_short": dict(first=_gpu(3, dtype=torch.int32)),
+    "alpha_rows": dict(alpha=_gpu(3, 8)),
+    "alpha_cols": dict(alpha=_gpu(4, 7)),
+    "target_rows": dict(target=_gpu(3, 8)),
+    "target_cols": dict(target=_gpu(4, 7)),
+    "buf_missing": dict(momentum=0.5),
+    "buf_rows": dict(momentum=0.5, buf=_gpu(3, 8)),
+    "buf_cols": dict(momentum=0.5, buf=_gpu(4, 7)),
+    "resid_alone": dict(resid_sq=_gpu(4, dtype=_F64)),
+    "resid_sq_short": dict(resid_sq=_gpu(3, dtype=_F64), alpha_sq=_gpu(4, dtype=_F64)),
+    "alpha_sq_dtype": dict(resid_sq=_gpu(4, dtype=_F64), alpha_sq=_gpu(4)),
+}
+MEAN_ERRORS = {k: v for k, v in ROUND_ERRORS.items() if "resid" not in k and "alpha_sq" not in k}
+MEAN_ERRORS.update({
+    "out_short": dict(out=_gpu(7)),
+    "out_dtype": dict(out=_gpu(8, dtype=_F64)),
+    "out_matrix": dict(out=_gpu(1, 8)),
+    "resid_total_short": dict(resid_total=_gpu(1, dtype=_F64)),
+    "resid_total_dtype": dict(resid_total=_gpu(2)),
+    "no_agents": dict(agents=_ids()),
+    "agents_repeated": dict(agents=_ids(1, 2, 1)),
+    "agents_out_of_range": dict(agents=_ids(0, 4)),
+    "agents_more_than_rows": dict(agents=_ids(0, 1, 2, 3, 0)),
+})
+
+
+@pytest.mark.parametrize("mean,case", [(False, c) for c in sorted(ROUND_ERRORS)] + [(True, c) for c in sorted(MEAN_ERRORS)])
+def test_fedadmm_spelling_raises_what_admm_ls_round_raises(mean, case, rec, monkeypatch):
+    """ops.admm_ls_round* and fed_ls_round*(..., "fedadmm") are two spellings
+    of one body: every argument error is the same exception with the same
+    text, apart from the wrapper's name."""
+    import contextlib
+    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())  # the distinct-agents check: no GPU
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    kw = dict(alpha=_gpu(4, 8), target=_gpu(4, 8))
+    if mean:
+        kw["out"] = _gpu(8)  # given, so that no default is allocated on a GPU
+    kw.update((MEAN_ERRORS if mean else ROUND_ERRORS)[case])
+    alpha, target = kw.pop("alpha"), kw.pop("target")
+    w, theta = _gpu(4, 8), _gpu(8)
+    admm, fed = (ops.admm_ls_round_mean, ops.fed_ls_round_mean) if mean else (ops.admm_ls_round, ops.fed_ls_round)
+    with pytest.raises(Exception) as a:
+        admm(w, alpha, target, theta, **kw)
+    with pytest.raises(Exception) as f:
+        fed(w, alpha, target, theta, "fedadmm", **kw)
+    assert type(a.value) is type(f.value) and isinstance(a.value, (ValueError, TypeError)), (a.value, f.value)
+    assert str(a.value).replace("admm_ls_round", "NAME") == str(f.value).replace("fed_ls_round", "NAME")
+    assert "NAME" not in str(a.value) and str(a.value)
+    assert rec.calls == []
+
+
 def test_ops_surface():
     assert ops.FED_ALGORITHMS == {"fedavg": 0, "fedprox": 1, "fedadmm": 2}
     assert {"dol_fed_ls_round_f32", "dol_fed_ls_round_mean_f32"} <= set(_native.SIGNATURES)
