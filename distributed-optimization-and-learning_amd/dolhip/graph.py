@@ -548,6 +548,22 @@ class MixingPlan:
             raise NotImplementedError("DGD rounds are fused into the sparse mixes; use a ring/CSR plan")
         return ops.dgd_csr(X, Y, self.rowptr, self.col, self.val, target, **kw)
 
+    def apply_gt(self, X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, target: torch.Tensor,
+                 self_weight: Optional[torch.Tensor] = None, objective: str = "least_squares", lr: float = 0.01,
+                 P: Optional[int] = None):
+        """One gradient-tracking round (ops.gt_ring / ops.gt_csr) with W = this
+        plan's W + diag(self_weight); ring or CSR.  A CSR plan that carries a
+        slab pack still runs ops.gt_csr: the LDS-gather kernel has no such
+        round.  Returns (XO, SO)."""
+        from . import ops
+        self._check_x(X)
+        kw = dict(self_weight=self_weight, objective=objective, lr=lr, P=P)
+        if self.kind == "ring":
+            return ops.gt_ring(X, S, XO, SO, self.w_prev, self.w_next, target, n_rows=self.n_rows, **kw)
+        if self.kind == "dense":
+            raise NotImplementedError("gradient-tracking rounds are fused into the sparse mixes; use a ring/CSR plan")
+        return ops.gt_csr(X, S, XO, SO, self.rowptr, self.col, self.val, target, **kw)
+
 
 def plans_for(graphs: Sequence[Graph], device, allow_ring: bool = True) -> List[MixingPlan]:
     return [MixingPlan.from_graph(g, device, allow_ring) for g in graphs]

@@ -1,10 +1,12 @@
 """Gradient tracking (DIGing / NEXT) for BASELINE config 3: one round in one
 HBM pass on the parameter-major bank (dol_gt_csr_pm_f32, any sparse W, at most
-ops.GT_MAX_AGENTS agents) and on the agent-major ring (dol_gt_ring_f32, any
-number of agents, and the blocks of a sharded ring through its halo form), and
-the device gradient of the separable losses (dol_separable_grad_f32) that
-starts the trackers.  ops re-exports the calls as ops.gt_csr_pm / ops.gt_ring
-/ ops.separable_grad.
+ops.GT_MAX_AGENTS agents), on the agent-major ring (dol_gt_ring_f32, any
+number of agents, and the blocks of a sharded ring through its halo form) and
+on the agent-major bank with any sparse W (dol_gt_csr_f32, any number of
+agents, and the column blocks of a column-sharded bank), and the device
+gradient of the separable losses (dol_separable_grad_f32) that starts the
+trackers.  ops re-exports the calls as ops.gt_csr_pm / ops.gt_ring /
+ops.gt_csr / ops.separable_grad.
 
   x_i' = sum_j W_ij x_j - lr s_i
   s_i' = sum_j W_ij s_j + grad f_i(x_i') - grad f_i(x_i)       s_i(0) = grad f_i(x_i(0))
@@ -17,7 +19,10 @@ validators of ops.py (_check_rows, _check_csr, _check_array) and pm_steps'
 square-W check, plus the four stated here: a known objective, at most
 ops.GT_MAX_AGENTS agents, four distinct state matrices and a self-weight
 vector of n floats; tests/test_gt_host.py pins them without a launch.
-gt_ring's own rules are in its docstring and in tests/test_gt_ring_host.py.
+gt_ring's own rules are in its docstring and in tests/test_gt_ring_host.py,
+gt_csr's in its docstring and in tests/test_gt_csr_host.py (those a CPU tensor
+reaches) and tests/test_gt_csr_gpu.py (the rest, with the library call
+recorded).
 """
 from __future__ import annotations
 
@@ -119,6 +124,43 @@ def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor
     _native.call("dol_gt_ring_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,
                  P, hp[0], hp[1], hp[2], hp[3], w_prev.data_ptr(), w_next.data_ptr(), _ops._ptr(self_weight),
                  target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
+    return XO, SO
+
+
+def gt_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, rowptr: torch.Tensor,
+           col: torch.Tensor, val: torch.Tensor, target: torch.Tensor, self_weight: Optional[torch.Tensor] = None,
+           objective: str = "least_squares", lr: float = 0.01,
+           P: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gt_csr_pm's round on the agent-major bank (dol_gt_csr_f32), for any
+    sparse W and any number of agents: X the parameters, S the trackers, target
+    the targets, [>= n, >= P] like mix_csr's X (n = rowptr length - 1); XO / SO
+    receive x' / s'.  W = W_off + diag(self_weight), W_off the square CSR
+    (normally with a zero diagonal).  Per coordinate
+      ax = mix of x, as = mix of s                     (mix_csr's sums)
+      ax = fl(ax + fl(d_i x_i)), as = fl(as + fl(d_i s_i))     with self_weight
+      x' = fma(-lr, s_i, ax);  s' = fl(fl(as + g(x', t_i)) - g(x_i, t_i))
+    the bits of gt_csr_pm on the same CSR and of gt_ring on a ring's CSR.  The
+    rules of this op: a known objective; the four state matrices distinct (a
+    Jacobi update of both); a self-weight vector of n floats; a square W.
+    Returns (XO, SO)."""
+    obj = _check_objective("gt_csr", objective)
+    n = rowptr.shape[0] - 1
+    state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
+    for i, (na, a) in enumerate(state):
+        for nb, b in state[i + 1:]:
+            if a is b or a.data_ptr() == b.data_ptr():
+                raise ValueError(f"gt_csr: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+    if self_weight is not None:
+        _ops._check_array("self_weight", self_weight, torch.float32, n, X.device)
+    P = X.shape[1] if P is None else P
+    ldx, ld_s, ldxo, ldso, ldt = (
+        _ops._check_rows(nm, t, P, n, f"{nm}: expected >= {n} rows on {{}}", 0, X.device)
+        for nm, t in state + (("target", target),))
+    _ops._check_csr(rowptr, col, val, X.device, same_length=False)
+    _check_square(rowptr, col, n)
+    _native.call("dol_gt_csr_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,
+                 P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
+                 _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
     return XO, SO
 
 

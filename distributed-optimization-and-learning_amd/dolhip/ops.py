@@ -1081,8 +1081,9 @@ from .scaffold import scaffold_ls_round  # noqa: E402,F401
 from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noqa: E402,F401
 
 # ---------------------------------------------------------------------------
-# Gradient tracking on the parameter-major bank and on the agent-major ring
-# (gt.py, which builds on the validators above and on pm_steps' square-W
-# check): gt_csr_pm, gt_ring, separable_grad.
+# Gradient tracking on the parameter-major bank, on the agent-major ring and
+# on the agent-major bank with any sparse W (gt.py, which builds on the
+# validators above and on pm_steps' square-W check): gt_csr_pm, gt_ring,
+# gt_csr, separable_grad.
 # ---------------------------------------------------------------------------
-from .gt import gt_csr_pm, gt_ring, separable_grad  # noqa: E402,F401
+from .gt import gt_csr, gt_csr_pm, gt_ring, separable_grad  # noqa: E402,F401

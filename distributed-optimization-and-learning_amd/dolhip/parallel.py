@@ -35,6 +35,7 @@ import torch.distributed as dist
 
 from . import ops
 from .bank import device_matrix, row_stride
+from .parallel_gt import column_sharded_gt_step
 
 # Fail fast instead of hanging: every collective of the engine's
 # process groups is bounded by this timeout.  The reference has no collectives
@@ -256,10 +257,13 @@ class ColumnSharded:
     """Mixing with ANY W sharded over the parameter dimension (one process per
     GPU).  x / y: local [N, ld] buffers holding columns [c0, c1) of every agent.
     `step()` = one Jacobi round; `dgd_step()` = one fused config-3 round with
-    the local `target` / `mom` blocks.  No collective on the data path."""
+    the local `target` / `mom` blocks; `gt_step()` = one gradient-tracking
+    round with the local tracker and `target` blocks.  No collective on the
+    data path."""
 
-    def __init__(self, plan, P: int, device, group=None, alloc: bool = True, apply=None, apply_dgd=None):
-        # apply / apply_dgd: kernel entries (default: the plan's HIP ops); tests inject a CPU checker
+    def __init__(self, plan, P: int, device, group=None, alloc: bool = True, apply=None, apply_dgd=None,
+                 apply_gt=None):
+        # apply / apply_dgd / apply_gt: kernel entries (default: the plan's HIP ops); tests inject a CPU checker
         self.plan = plan
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -269,14 +273,22 @@ class ColumnSharded:
         self.Pl = self.c1 - self.c0
         self.device = torch.device(device)
         self.ld = row_stride(max(self.Pl, 1))
-        self._injected = (apply, apply_dgd)  # kept across set_plan (the tests' CPU checkers)
-        self._apply = apply if apply is not None else plan.apply
-        self._apply_dgd = apply_dgd if apply_dgd is not None else plan.apply_dgd
+        self._injected = (apply, apply_dgd, apply_gt)  # kept across set_plan (the tests' CPU checkers)
+        self._bind(plan)
         if alloc:
             self.x = torch.empty(self.N, self.ld, dtype=torch.float32, device=self.device)
             self.y = torch.empty_like(self.x)
 
-    def set_plan(self, plan, apply=None, apply_dgd=None) -> None:
+    def _bind(self, plan) -> None:
+        """The round entries: the injected ones, else `plan`'s HIP ops.  (A plan
+        without a gradient-tracking entry, such as a test's stand-in, leaves
+        gt_step unbound.)"""
+        inj_apply, inj_dgd, inj_gt = self._injected
+        self._apply = inj_apply if inj_apply is not None else plan.apply
+        self._apply_dgd = inj_dgd if inj_dgd is not None else plan.apply_dgd
+        self._apply_gt = inj_gt if inj_gt is not None else getattr(plan, "apply_gt", None)
+
+    def set_plan(self, plan, apply=None, apply_dgd=None, apply_gt=None) -> None:
         """A new W for the next rounds (time-varying graphs, BASELINE config 5:
         every rank draws the same W from the round's seed); same agent count.
         Entries injected at construction (or passed here) stay in use; the
@@ -284,12 +296,9 @@ class ColumnSharded:
         if (plan.n_rows, plan.n_cols) != (self.N, self.plan.n_cols):
             raise ValueError("set_plan: the new W must have the same shape")
         self.plan = plan
-        if apply is not None or apply_dgd is not None:
-            self._injected = (apply if apply is not None else self._injected[0],
-                              apply_dgd if apply_dgd is not None else self._injected[1])
-        inj_apply, inj_dgd = self._injected
-        self._apply = inj_apply if inj_apply is not None else plan.apply
-        self._apply_dgd = inj_dgd if inj_dgd is not None else plan.apply_dgd
+        self._injected = tuple(new if new is not None else old
+                               for new, old in zip((apply, apply_dgd, apply_gt), self._injected))
+        self._bind(plan)
 
     def local_cols(self, full: torch.Tensor) -> torch.Tensor:
         """This rank's column block of a full [N, >=P] matrix."""
@@ -305,9 +314,14 @@ class ColumnSharded:
             self._apply_dgd(self.x, self.y, target, mom=mom, P=self.Pl, **kw)
         self.x, self.y = self.y, self.x
 
-    def gather(self, dst: int = 0) -> Optional[torch.Tensor]:
-        """Full [N, P] on rank `dst` (checkpoints / tests; not on the round path)."""
-        mine = self.x[:, :self.Pl].contiguous()
+    # gt_step(s, s_out, target, **kw): one gradient-tracking round on the rank's
+    # column block; swaps x / y and returns the tracker pair swapped, (s_out, s)
+    gt_step = column_sharded_gt_step
+
+    def gather(self, dst: int = 0, src: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """Full [N, P] on rank `dst` (checkpoints / tests; not on the round
+        path) of x, or of `src`, another local [N, >= Pl] block."""
+        mine = (self.x if src is None else src)[:, :self.Pl].contiguous()
         if self.world == 1:
             return mine
         staged = mine.device.type == "cuda" and _backend(self.group) == "gloo"

@@ -752,32 +752,30 @@ def ring_gt_weights(ring_csr):
     return ring[0], ring[1], d
 
 
-class SeparableGT:
-    """Config 3 with gradient tracking on the agent-major ring, SeparableGTPM's
+class SeparableGTCSR:
+    """Config 3 with gradient tracking on the agent-major bank, SeparableGTPM's
     sibling on SeparableDGD's bank: the same round (see SeparableGTPM), one
-    kernel and one pass over X, S and the targets (dol_gt_ring_f32), for any
-    number of agents -- the parameter-major round stops at ops.GT_MAX_AGENTS.
-    Not a reference algorithm.
+    kernel and one pass over X, S and the targets through plan.apply_gt
+    (dol_gt_csr_f32 on a CSR plan, dol_gt_ring_f32 on a ring plan), for any
+    sparse W and any number of agents -- the parameter-major round stops at
+    ops.GT_MAX_AGENTS.  Not a reference algorithm.
 
-    plan must be a ring plan (plan.kind == "ring": its w_prev / w_next are the
-    stencil); W = that stencil + diag(self_weight) must be doubly stochastic
-    with a positive diagonal, which ring_gt_weights gives.  lr must be small
-    against the spectral gap of W, which shrinks as 1 / n^2 on a ring: on 9
-    agents with Metropolis weights, least squares, 0.1 converges in 200 rounds
-    and 0.3 diverges; 33 agents need far more rounds (a float32 CPU simulation
-    of this arithmetic).
+    plan is any non-dense plan; W = its W + diag(self_weight) must be doubly
+    stochastic with a positive diagonal, which graph.metropolis_weights gives
+    from any symmetric pattern.  lr must be small against the spectral gap of
+    W (SeparableGTPM's docstring has the 16-agent random 4-regular numbers).
 
     The bank holds x / y (parameters in and out), s / s_out (trackers) and
     target, with SeparableDGD's seeded init; s starts as ops.separable_grad(x,
-    target).  The parameter-major draw of SeparableGTPM is another element
-    order: SeparableGTPM.from_agent_major makes the same problem there."""
+    target).  With the same seed and shape it is the problem of SeparableDGD
+    and of SeparableGT, bit for bit.  The parameter-major draw of SeparableGTPM
+    is another element order: SeparableGTPM.from_agent_major makes the same
+    problem there."""
 
     def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
                  self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
         from . import ops
-        if plan.kind != "ring":
-            raise ValueError(f"SeparableGT runs on a ring plan (got kind {plan.kind!r}); SeparableGTPM takes any "
-                             f"sparse W of up to {ops.GT_MAX_AGENTS} agents")
+        self._check_plan(plan)
         if objective not in ops.OBJECTIVES:
             raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
         self.plan, self.objective, self.lr = plan, objective, float(lr)
@@ -801,13 +799,16 @@ class SeparableGT:
         ops.separable_grad(self.bank.rows("x"), self.bank.rows("target"), self.bank.rows("s"), objective)
         self.rounds = 0
 
+    @staticmethod
+    def _check_plan(plan) -> None:
+        if plan.kind == "dense":
+            raise ValueError("the gradient-tracking round mixes a sparse (CSR) W")
+
     def round(self) -> None:
         """One gradient-tracking round (one kernel); swaps x / y and s / s_out."""
-        from . import ops
-        b, p = self.bank, self.plan
-        ops.gt_ring(b.buffer("x"), b.buffer("s"), b.buffer("y"), b.buffer("s_out"), p.w_prev, p.w_next,
-                    b.buffer("target"), self_weight=self.self_weight, objective=self.objective, lr=self.lr, P=self.P,
-                    n_rows=self.N)
+        b = self.bank
+        self.plan.apply_gt(b.buffer("x"), b.buffer("s"), b.buffer("y"), b.buffer("s_out"), b.buffer("target"),
+                           self_weight=self.self_weight, objective=self.objective, lr=self.lr, P=self.P)
         b.swap("x", "y")
         b.swap("s", "s_out")
         self.rounds += 1
@@ -832,6 +833,27 @@ class SeparableGT:
             raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
         opt = self.targets().double().mean(0, keepdim=True)
         return float((self.params().double() - opt).abs().max())
+
+
+class SeparableGT(SeparableGTCSR):
+    """SeparableGTCSR on the agent-major ring only: one kernel and one pass
+    over X, S and the targets (dol_gt_ring_f32), for any number of agents.
+    Not a reference algorithm.
+
+    plan must be a ring plan (plan.kind == "ring": its w_prev / w_next are the
+    stencil); W = that stencil + diag(self_weight) must be doubly stochastic
+    with a positive diagonal, which ring_gt_weights gives.  lr must be small
+    against the spectral gap of W, which shrinks as 1 / n^2 on a ring: on 9
+    agents with Metropolis weights, least squares, 0.1 converges in 200 rounds
+    and 0.3 diverges; 33 agents need far more rounds (a float32 CPU simulation
+    of this arithmetic).  Bank, init and accessors are SeparableGTCSR's."""
+
+    @staticmethod
+    def _check_plan(plan) -> None:
+        from . import ops
+        if plan.kind != "ring":
+            raise ValueError(f"SeparableGT runs on a ring plan (got kind {plan.kind!r}); SeparableGTPM takes any "
+                             f"sparse W of up to {ops.GT_MAX_AGENTS} agents")
 
 
 class TimeVaryingMLPGossip:

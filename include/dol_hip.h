@@ -413,6 +413,38 @@ int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, fl
                     float lr, hipStream_t s);
 
 /*
+ * One gradient-tracking round (DIGing / NEXT) of BASELINE config 3 on the
+ * agent-major bank with any sparse W in one pass: dol_gt_csr_pm_f32's round in
+ * dol_mix_csr_f32's layout, for any number of agents (no 4096 cap) and for the
+ * column blocks of a column-sharded bank.  Not in the reference: it replaces
+ * the consensus + local step round of DIST/simulators.py:147-162 (a biased
+ * fixed point under a constant step size); the mix inside is its consensus
+ * (DIST/clients.py:61-69) in dol_mix_csr_f32's rounding.  X (parameters), S
+ * (trackers), XO, SO and target are row matrices of n rows; W = W_off +
+ * diag(self_w), W_off the square CSR (0 <= col < n, normally a zero diagonal).
+ * For every row i and column c, all fp32, each operation rounded once:
+ *   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e, product and sum rounded separately)
+ *   as = the same over s
+ *   self_w != NULL:  ax = fl(ax + fl(self_w[i]*x_i));  as = fl(as + fl(self_w[i]*s_i))
+ *   x' = fma(-lr, s_i, ax)
+ *   s' = fl(fl(as + g(x', t_i)) - g(x_i, t_i))           g as dol_separable_grad_f32
+ * the bits of dol_gt_csr_pm_f32 on the same CSR, and of dol_gt_ring_f32 on a
+ * ring's CSR.  n < 0 or P < 0: DOL_EINVAL.  n == 0 or P == 0: DOL_OK, nothing
+ * launched.  No null pointers but self_w (col and val are refused when null, as
+ * dol_gt_csr_pm_f32 refuses them); every ld >= P; X, S, XO, SO pairwise
+ * distinct (a Jacobi update of both); objective 0 or 1; a problem whose launch
+ * would exceed 2^24 blocks is refused as dol_mix_csr_f32 refuses it.  Any n
+ * that fits int32.  16-B columns where the five matrices are 16-B aligned with
+ * ld % 4 == 0, else scalar.  The round reads rowptr / col / val once for both
+ * gathers and streams X, S, target in and XO, SO out once.  Stream-ordered;
+ * allocates nothing; does not synchronise.
+ */
+int dol_gt_csr_f32(const float* X, int64_t ldx, const float* S, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                   int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col, const float* val,
+                   const float* self_w /* nullable */, const float* target, int64_t ldt, int32_t objective,
+                   float lr, hipStream_t s);
+
+/*
  * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the
  * separable losses of dol_dgd_ring_f32 (objective 0: fl(x - t), 1:
  * -t / (1 + exp(t x)), the same device code).  Elementwise, so it serves the
