@@ -114,6 +114,36 @@ inline int check_rows(const char* nm, bool negative, bool empty, bool null, bool
   } while (0)
 constexpr const char* kJacobiAlias = "X and Y alias (Jacobi mix needs two buffers)";
 
+// The five row matrices of a gradient-tracking round on an agent-major bank
+// (X, S in; XO, SO out; the targets T) and the argument rules that
+// dol_gt_ring_f32 and dol_gt_csr_f32 share, each written once.  An entry point
+// calls check(), then its own rules (the ring's halos), then objective_ok(),
+// and hands vec_ok() to split_cols.  (dol_gt_csr_pm_f32 validates for itself:
+// gt_csr_pm_impl in pmajor.hip has other rules, in another order.)
+struct GtRows {
+  const float* X; int64_t ldx;
+  const float* S; int64_t lds;
+  float* XO; int64_t ldxo;
+  float* SO; int64_t ldso;
+  const float* T; int64_t ldt;
+
+  // n rows of P columns; other_null: one of the entry point's own required pointers is null
+  int check(const char* nm, int32_t n, int64_t P, bool other_null) const {
+    DOL_DIMS_OK(nm, ldx, lds, ldxo, ldso, ldt, P);
+    const bool alias = X == S || X == XO || X == SO || S == XO || S == SO || XO == SO;
+    return check_rows(nm, n < 0 || P < 0, n == 0 || P == 0, !X || !S || !XO || !SO || !T || other_null,
+                      ldx < P || lds < P || ldxo < P || ldso < P || ldt < P, alias,
+                      "X, S, XO, SO alias (the Jacobi update of x and s needs four buffers)");
+  }
+  static int objective_ok(const char* nm, int32_t objective) {
+    return objective != 0 && objective != 1 ? fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm) : DOL_OK;
+  }
+  bool vec_ok() const {
+    return row_vec_ok(X, ldx) && row_vec_ok(S, lds) && row_vec_ok(XO, ldxo) && row_vec_ok(SO, ldso) &&
+           row_vec_ok(T, ldt);
+  }
+};
+
 // ----------------------------------------------------------------------------
 // vector helpers: the same kernel body runs on float (tail / unaligned) and
 // f4 (main stream).  All arithmetic is explicit per lane so that each
@@ -190,6 +220,41 @@ template <int OBJ>
 __device__ __forceinline__ float separable_grad(float x, float t) {
   if constexpr (OBJ == 0) return x - t;
   else return -t / (1.0f + expf(t * x));
+}
+
+// The gradient-tracking round (DIGing / NEXT) on one coordinate after its two
+// mixes ax = (W_off x), as = (W_off s): the one place this arithmetic is written
+// (csr_pm_gt_kernel, gt_ring_*_kernel, gt_csr_*_kernel), which is why the three
+// rounds agree bit for bit whenever their mixes do.  All fp32, each operation
+// rounded once (-ffp-contract=off), d the agent's self weight:
+//   self:  ax = fl(ax + fl(d x));  as = fl(as + fl(d s))
+//   x' = fma(-lr, s, ax)
+//   s' = fl(fl(as + g(x', t)) - g(x, t))                     g = separable_grad<OBJ>
+// self is a compile-time constant on the agent-major banks and the kernel's
+// run-time "self weights given" on the parameter-major one.
+template <int OBJ>
+__device__ __forceinline__ void gt_finish(float ax, float as, float x, float s, float t, float d, bool self,
+                                          float neg_lr, float& xo, float& so) {
+  if (self) {
+    ax = ax + d * x;
+    as = as + d * s;
+  }
+  xo = __builtin_fmaf(neg_lr, s, ax);
+  so = (as + separable_grad<OBJ>(xo, t)) - separable_grad<OBJ>(x, t);
+}
+// the same on four coordinates; d: one agent's weight (agent-major) or four agents' (parameter-major)
+template <int OBJ, class D>
+__device__ __forceinline__ void gt_finish(f4 ax, f4 as, f4 x, f4 s, f4 t, D d, bool self, float neg_lr, f4& xo,
+                                          f4& so) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float dj, xe, se;
+    if constexpr (std::is_same_v<D, f4>) dj = d[j];
+    else dj = d;
+    gt_finish<OBJ>(ax[j], as[j], x[j], s[j], t[j], dj, self, neg_lr, xe, se);
+    xo[j] = xe;
+    so[j] = se;
+  }
 }
 
 // The local steps on one coordinate: the one place this arithmetic is written

@@ -10,13 +10,12 @@
 // row t_i ride along.  For every row i and column c, all fp32, each operation
 // rounded once (-ffp-contract=off):
 //   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e: fmac())     as = the same over s
-//   self_w:  ax = fl(ax + fl(self_w[i] x_i));  as = fl(as + fl(self_w[i] s_i))
-//   x' = fma(-lr, s_i, ax)
-//   s' = fl(fl(as + g(x', t_i)) - g(x_i, t_i))                 g = separable_grad<OBJ>
-// the bits of dol_gt_csr_pm_f32 on the same CSR, and of dol_gt_ring_f32 on a
-// ring's CSR.  The Epi hook of csr_xcd_kernel / csr_mix_kernel cannot say this:
-// an epilogue sees one mixed value, this round needs two mixes through one
-// index and the centre rows of both (gt_ring.hip's header, for the ring).
+// and then gt_finish (dol_launch.h) with d = self_w[i], the lane that
+// dol_gt_csr_pm_f32 and dol_gt_ring_f32 run too: the same bits as the first on
+// the same CSR and as the second on a ring's CSR.  The Epi hook of
+// csr_xcd_kernel / csr_mix_kernel cannot say this: an epilogue sees one mixed
+// value, this round needs two mixes through one index and the centre rows of
+// both (gt_ring.hip's header, for the ring).
 //
 // Policies: the gathered rows and the centre rows load with the default policy
 // (a centre row is some other row's neighbour); the target row is read once and
@@ -36,7 +35,7 @@
 //   8192    2^20 + 2048   44.48 / 44.75    47.56 / 47.87    31.51
 // 512 B wins by 5-7 % on padded rows at both sizes and ties (0.4 % behind) on
 // ld = 2^20; one width stays and the switch is gone.  The counters
-// (tools/gt_csr_counters.py, profiles/gt_csr_counters.json; FETCH_SIZE x 2
+// (tools/gt_counters.py, profiles/gt_csr_counters.json; FETCH_SIZE x 2
 // against 3 N P 4) read 1.78 x the algorithmic bytes at 1024 agents and 2.48 x
 // at 8192, written 1.000 x: gather re-reads do leave L2, most of them at 8192
 // agents, yet halving the footprint bought no time there, so they are served
@@ -68,40 +67,6 @@ struct GtCsr {
 // (rowptr, col, val and the self weights are kernel arguments of their own,
 // const __restrict__, as in csr.hip and gt_ring.hip)
 
-// The round's arithmetic after the two mixes, on one coordinate.
-template <int OBJ, bool SELF>
-__device__ __forceinline__ void gt_csr_lane(float ax, float as, float x, float s, float t, float ws, float neg_lr,
-                                            float& xo, float& so) {
-  if constexpr (SELF) {
-    ax = ax + ws * x;
-    as = as + ws * s;
-  }
-  xo = __builtin_fmaf(neg_lr, s, ax);
-  so = (as + separable_grad<OBJ>(xo, t)) - separable_grad<OBJ>(x, t);
-}
-template <int OBJ, bool SELF>
-__device__ __forceinline__ void gt_csr_finish(float ax, float as, float x, float s, float t, float ws, float neg_lr,
-                                              float& xo, float& so) {
-  gt_csr_lane<OBJ, SELF>(ax, as, x, s, t, ws, neg_lr, xo, so);
-}
-template <int OBJ, bool SELF>
-__device__ __forceinline__ void gt_csr_finish(f4 ax, f4 as, f4 x, f4 s, f4 t, float ws, float neg_lr, f4& xo,
-                                              f4& so) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    float xe, se;
-    gt_csr_lane<OBJ, SELF>(ax[j], as[j], x[j], s[j], t[j], ws, neg_lr, xe, se);
-    xo[j] = xe;
-    so[j] = se;
-  }
-}
-
-template <typename V>
-__device__ __forceinline__ V ld_target(const V* p) {
-  if constexpr (sizeof(V) == 16) return __builtin_nontemporal_load(p);
-  else return *p;
-}
-
 // ----------------------------------------------------------------------------
 // 4 KiB column tiles (V = f4: 256 lanes x 16 B) or 1 KiB of scalar columns (V =
 // float: the P % 4 tail, or every column when a row base is not 16-B aligned),
@@ -128,7 +93,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, i
   auto xat = [&](int64_t r) { return *reinterpret_cast<const V*>(xb + r * a.ldx); };
   auto sat = [&](int64_t r) { return *reinterpret_cast<const V*>(sb + r * a.lds); };
   for (int r = r0; r < r1; ++r) {
-    const V t = ld_target(reinterpret_cast<const V*>(a.T + int64_t(r) * a.ldt + cf));
+    const V t = ldv<V, sizeof(V) == 16>(reinterpret_cast<const V*>(a.T + int64_t(r) * a.ldt + cf));
     const V xc = xat(r), sc = sat(r);
     const float ws = SELF ? wself[r] : 0.0f;
     const int e0 = rowptr[r];
@@ -156,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, i
       as = fmac(as, v, sat(cj));
     }
     V xo, so;
-    gt_csr_finish<OBJ, SELF>(ax, as, xc, sc, t, ws, a.neg_lr, xo, so);
+    gt_finish<OBJ>(ax, as, xc, sc, t, ws, SELF, a.neg_lr, xo, so);
     __builtin_nontemporal_store(xo, reinterpret_cast<V*>(a.XO + int64_t(r) * a.ldxo + cf));
     __builtin_nontemporal_store(so, reinterpret_cast<V*>(a.SO + int64_t(r) * a.ldso + cf));
   }
@@ -243,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_row
           as = fmac(as, vv[p][q], ss[p][q]);
         }
         f4 xo, so;
-        gt_csr_finish<OBJ, SELF>(ax, as, xc[p], sc[p], tv[p], ws[p], a.neg_lr, xo, so);
+        gt_finish<OBJ>(ax, as, xc[p], sc[p], tv[p], ws[p], SELF, a.neg_lr, xo, so);
         __builtin_nontemporal_store(xo, reinterpret_cast<f4*>(a.XO + int64_t(rr[p]) * a.ldxo) + c);
         __builtin_nontemporal_store(so, reinterpret_cast<f4*>(a.SO + int64_t(rr[p]) * a.ldso) + c);
       }
@@ -277,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_row
         as = fmac(as, v, sb[cj * ldsv]);
       }
       f4 xo, so;
-      gt_csr_finish<OBJ, SELF>(ax, as, xc[p], sc[p], tv[p], ws[p], a.neg_lr, xo, so);
+      gt_finish<OBJ>(ax, as, xc[p], sc[p], tv[p], ws[p], SELF, a.neg_lr, xo, so);
       __builtin_nontemporal_store(xo, reinterpret_cast<f4*>(a.XO + int64_t(r) * a.ldxo) + c);
       __builtin_nontemporal_store(so, reinterpret_cast<f4*>(a.SO + int64_t(r) * a.ldso) + c);
     }
@@ -301,16 +266,10 @@ int dol_gt_csr_f32(const float* X, int64_t ldx, const float* S, int64_t lds, flo
                    const float* self_w, const float* target, int64_t ldt, int32_t objective, float lr,
                    hipStream_t s) {
   const char* nm = "dol_gt_csr_f32";
-  DOL_DIMS_OK(nm, ldx, lds, ldxo, ldso, ldt, P);
-  const bool alias = X == S || X == XO || X == SO || S == XO || S == SO || XO == SO;
-  DOL_CHECKED(check_rows(nm, n < 0 || P < 0, n == 0 || P == 0,
-                         !X || !S || !XO || !SO || !target || !rowptr || !col || !val,
-                         ldx < P || lds < P || ldxo < P || ldso < P || ldt < P, alias,
-                         "X, S, XO, SO alias (the Jacobi update of x and s needs four buffers)"));
-  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
-  const bool vec_ok = row_vec_ok(X, ldx) && row_vec_ok(S, lds) && row_vec_ok(XO, ldxo) && row_vec_ok(SO, ldso) &&
-                      row_vec_ok(target, ldt);
-  const ColSplit cs = split_cols(P, vec_ok);
+  const GtRows m{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt};
+  DOL_CHECKED(m.check(nm, n, P, !rowptr || !col || !val));
+  if (const int rc = GtRows::objective_ok(nm, objective)) return rc;
+  const ColSplit cs = split_cols(P, m.vec_ok());
   constexpr int XW = 32, XPASSES = 2;  // XCD-pinned tiles: 512 B of a row, 16 rows per block
   const int64_t n_rg = cdiv(n, kGtCsrRows);
   if (mul_sat(cdiv(cs.n4, kThreads), n_rg) > kMaxBlocks || mul_sat(cdiv(cs.tail, kThreads), n_rg) > kMaxBlocks)

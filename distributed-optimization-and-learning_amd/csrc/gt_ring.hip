@@ -9,15 +9,13 @@
 // fp32, each operation rounded once (-ffp-contract=off):
 //   ax = fl(fl(+0 + fl(wp[r] x[r-1])) + fl(wn[r] x[r+1]))     axpy0, as dol_mix_ring_f32
 //   as = the same over s
-//   w_self:  ax = fl(ax + fl(ws[r] x[r]));  as = fl(as + fl(ws[r] s[r]))
-//   x' = fma(-lr, s[r], ax)
-//   s' = fl(fl(as + g(x', t[r])) - g(x[r], t[r]))              g = separable_grad<OBJ>
-// which are the bits of dol_gt_csr_pm_f32 on the ring's CSR with the same
-// self weights: the CSR sums the two neighbours in ascending column order,
-// here it is previous then next, and fl(fl(+0 + a) + b) commutes in a and b
-// (dol_mix_ring_f32's argument).  The Epi hook of ring_mix_dma_kernel cannot
-// say this: an epilogue sees one mixed value, this round needs two and the
-// centre rows of both.
+// and then gt_finish (dol_launch.h) with d = w_self[r], the lane that
+// dol_gt_csr_pm_f32 runs too: the same bits as that round on the ring's CSR
+// with the same self weights, because the CSR sums the two neighbours in
+// ascending column order, here it is previous then next, and fl(fl(+0 + a) + b)
+// commutes in a and b (dol_mix_ring_f32's argument).  The Epi hook of
+// ring_mix_dma_kernel cannot say this: an epilogue sees one mixed value, this
+// round needs two and the centre rows of both.
 #include "dol_launch.h"
 
 namespace {
@@ -29,14 +27,7 @@ constexpr int kGtPanel = 512;   // column tiles per panel of its block order (a 
 template <int OBJ, bool SELF>
 __device__ __forceinline__ void gt_ring_lane(float xp, float x, float xn, float sp, float s, float sn, float t,
                                              float wp, float wn, float ws, float neg_lr, float& xo, float& so) {
-  float ax = axpy0(wp, xp, wn, xn);
-  float as = axpy0(wp, sp, wn, sn);
-  if constexpr (SELF) {
-    ax = ax + ws * x;
-    as = as + ws * s;
-  }
-  xo = __builtin_fmaf(neg_lr, s, ax);
-  so = (as + separable_grad<OBJ>(xo, t)) - separable_grad<OBJ>(x, t);
+  gt_finish<OBJ>(axpy0(wp, xp, wn, xn), axpy0(wp, sp, wn, sn), x, s, t, ws, SELF, neg_lr, xo, so);
 }
 
 struct GtRing {
@@ -48,6 +39,13 @@ struct GtRing {
   const float* xhp; const float* xhn;  // row -1 and row n_rows of X (the wrap-around rows without halos)
   const float* shp; const float* shn;  // the same of S
   float neg_lr;
+  // row r of X / of S, r in [-1, n]: the matrix row, or the halo on its side
+  __device__ __forceinline__ const float* xrow(int r, int n) const { return pick(X, ldx, xhp, xhn, r, n); }
+  __device__ __forceinline__ const float* srow(int r, int n) const { return pick(S, lds, shp, shn, r, n); }
+  static __device__ __forceinline__ const float* pick(const float* M, int64_t ld, const float* hp, const float* hn,
+                                                      int r, int n) {
+    return (r < 0) ? hp : (r >= n ? hn : M + int64_t(r) * ld);
+  }
 };
 // (the weight vectors are kernel arguments of their own, const __restrict__: the
 // compiler then reads them with scalar loads, ahead of the DMA wait)
@@ -72,7 +70,7 @@ struct GtRing {
 // XCDs, a vertical neighbour is kGtPanel / 8 = 64 blocks later on the same XCD
 // (kGtPanel % 8 == 0), inside the 96 resident there.  Measured at 1024 x 2^20,
 // ld = 2^20 + 2048, one box, (a) / dgd_ring pairs and the read ratio
-// (tools/gt_ring_ab.py, profiles/gt_ring_ab.jsonl): no panels 1.017 / 1.147;
+// (tools/gt_ab.py, profiles/gt_ring_ab.jsonl): no panels 1.017 / 1.147;
 // 64 1.167 / 1.0014; 128 1.175 / 1.0015; 256 1.11 / 1.0014; 512 0.965-1.008 /
 // 1.0017; 768 1.05 / 1.035; 1024 1.02 / 1.13.  Narrow panels hit L2 as well but
 // stream shorter runs of each row.
@@ -106,21 +104,15 @@ __global__ __launch_bounds__(kThreads) void gt_ring_dma_kernel(GtRing a, const f
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t c = int64_t(ct) * kThreads + threadIdx.x;  // f4 column
   if (c >= ncols_v) return;
-  auto xrow = [&](int r) -> const float* {
-    return (r < 0) ? a.xhp : (r >= n_rows ? a.xhn : a.X + int64_t(r) * a.ldx);
-  };
-  auto srow = [&](int r) -> const float* {
-    return (r < 0) ? a.shp : (r >= n_rows ? a.shn : a.S + int64_t(r) * a.lds);
-  };
 #pragma unroll
   for (int k = 0; k < R + 2; ++k) {
     const int r = min(r0 - 1 + k, r1);
     if (k >= 2 && k < R) {  // rows no other tile reads: nontemporal
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(xrow(r) + 4 * c), DOL_LPTR(&lds[wave][0][k][0]), 16, 0, 2);
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(srow(r) + 4 * c), DOL_LPTR(&lds[wave][1][k][0]), 16, 0, 2);
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(a.xrow(r, n_rows) + 4 * c), DOL_LPTR(&lds[wave][0][k][0]), 16, 0, 2);
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(a.srow(r, n_rows) + 4 * c), DOL_LPTR(&lds[wave][1][k][0]), 16, 0, 2);
     } else {
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(xrow(r) + 4 * c), DOL_LPTR(&lds[wave][0][k][0]), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(DOL_GPTR(srow(r) + 4 * c), DOL_LPTR(&lds[wave][1][k][0]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(a.xrow(r, n_rows) + 4 * c), DOL_LPTR(&lds[wave][0][k][0]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(a.srow(r, n_rows) + 4 * c), DOL_LPTR(&lds[wave][1][k][0]), 16, 0, 0);
     }
   }
   f4 tv[R];  // the target rows and the weights ride with the DMA
@@ -177,12 +169,8 @@ __global__ __launch_bounds__(kThreads) void gt_ring_kernel(GtRing a, const float
   const int r0 = static_cast<int>(b / nct) * kGtTailRows;
   const int r1 = min(r0 + kGtTailRows, n_rows);
   const int64_t cf = c_off + c;
-  auto xat = [&](int r) {
-    return ((r < 0) ? a.xhp : (r >= n_rows ? a.xhn : a.X + int64_t(r) * a.ldx))[cf];
-  };
-  auto sat = [&](int r) {
-    return ((r < 0) ? a.shp : (r >= n_rows ? a.shn : a.S + int64_t(r) * a.lds))[cf];
-  };
+  auto xat = [&](int r) { return a.xrow(r, n_rows)[cf]; };
+  auto sat = [&](int r) { return a.srow(r, n_rows)[cf]; };
   float xp = xat(r0 - 1), x = xat(r0), sp = sat(r0 - 1), s = sat(r0);
   for (int r = r0; r < r1; ++r) {
     const float xn = xat(r + 1), sn = sat(r + 1);
@@ -205,12 +193,8 @@ int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, fl
                     const float* w_self, const float* target, int64_t ldt, int32_t objective, float lr,
                     hipStream_t s) {
   const char* nm = "dol_gt_ring_f32";
-  DOL_DIMS_OK(nm, ldx, lds, ldxo, ldso, ldt, P);
-  const bool alias = X == S || X == XO || X == SO || S == XO || S == SO || XO == SO;
-  DOL_CHECKED(check_rows(nm, n_rows < 0 || P < 0, n_rows == 0 || P == 0,
-                         !X || !S || !XO || !SO || !w_prev || !w_next || !target,
-                         ldx < P || lds < P || ldxo < P || ldso < P || ldt < P, alias,
-                         "X, S, XO, SO alias (the Jacobi update of x and s needs four buffers)"));
+  const GtRows m{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt};
+  DOL_CHECKED(m.check(nm, n_rows, P, !w_prev || !w_next));
   const int n_halos = (x_halo_prev != nullptr) + (x_halo_next != nullptr) + (s_halo_prev != nullptr) +
                       (s_halo_next != nullptr);
   if (n_halos != 0 && n_halos != 4) return fail(DOL_EINVAL, "%s: pass all four halos or none", nm);
@@ -221,10 +205,9 @@ int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, fl
     s_halo_prev = S + int64_t(n_rows - 1) * lds;
     s_halo_next = S;
   }
-  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
-  const bool vec_ok = row_vec_ok(X, ldx) && row_vec_ok(S, lds) && row_vec_ok(XO, ldxo) && row_vec_ok(SO, ldso) &&
-                      row_vec_ok(target, ldt) && aligned16(x_halo_prev) && aligned16(x_halo_next) &&
-                      aligned16(s_halo_prev) && aligned16(s_halo_next);
+  if (const int rc = GtRows::objective_ok(nm, objective)) return rc;
+  const bool vec_ok = m.vec_ok() && aligned16(x_halo_prev) && aligned16(x_halo_next) && aligned16(s_halo_prev) &&
+                      aligned16(s_halo_next);
   const ColSplit cs = split_cols(P, vec_ok);
   constexpr int R = kGtRows;
   const int64_t nct4 = cdiv(cs.n4, kThreads), nctt = cdiv(cs.tail, kThreads);

@@ -61,7 +61,7 @@
 //   80 KiB x 2  3.88 / 4.71 (3.67 / 4.65)     <- least squares
 //   64 KiB x 2  4.17 / 4.47 (4.17 / 4.46)
 //   48 KiB x 3  4.23 / 4.42 (4.23 / 4.43)     <- logistic
-// Legs (tools/gt_pm_ab.py, profiles/gt_pm_ab.jsonl; one process, same buffers,
+// Legs (tools/gt_ab.py, profiles/gt_pm_ab.jsonl; one process, same buffers,
 // medians of 5 windows): (a) the round composed from two mixes, two gradient
 // passes and the elementwise ops, (b) this kernel, (c) the least-squares +
 // momentum DGD round above (the same five streams); HBM = 5 N P 4 bytes over
@@ -477,9 +477,8 @@ __global__ __launch_bounds__(T) void csr_pm_steps_kernel(const float* __restrict
 // decentralised optimiser beyond the consensus round (DIST/simulators.py:
 // 147-162); the mix is its consensus (DIST/clients.py:61-69).  Per coordinate:
 //   ax = mix_quad over the X image, as = mix_quad over the S image (same Quad)
-//   self weights:  ax = fl(ax + fl(d x)),  as = fl(as + fl(d s))
-//   x' = fma(-lr, s, ax);   s' = fl(fl(as + g(x', t)) - g(x, t))
-// g = separable_grad<OBJ> (dol_launch.h).  A stage holds sr p-rows of three
+// and then gt_finish (dol_launch.h), the lane the agent-major rounds of
+// gt_ring.hip and gt_csr.hip run too.  A stage holds sr p-rows of three
 // images -- X and S xw floats each (both are gathered), T nw floats -- that
 // come in by one LDS-DMA ring; the agent's own x, s, t are f4 LDS reads of the
 // same images, so no gradient matrix is stored or streamed: X, S, T in, X', S'
@@ -501,17 +500,6 @@ __device__ __forceinline__ f4 load_self_weights(const float* __restrict__ D, int
 #pragma unroll
   for (int a = 0; a < 4; ++a) d[a] = D[min(4 * q + a, n_rows - 1)];
   return f4{d[0], d[1], d[2], d[3]};
-}
-
-template <int OBJ>
-__device__ __forceinline__ void gt_lane(float ax, float as, float x, float s, float t, float d, bool self,
-                                        float neg_lr, float& xo, float& so) {
-  if (self) {
-    ax = ax + d * x;
-    as = as + d * s;
-  }
-  xo = __builtin_fmaf(neg_lr, s, ax);
-  so = (as + separable_grad<OBJ>(xo, t)) - separable_grad<OBJ>(x, t);
 }
 
 // One stage of the round: the X images at im0, the S images behind them, the
@@ -542,12 +530,8 @@ __device__ __forceinline__ void gt_stage(const Quad (&Q)[1], f4 dw, const float*
     const f4 xv = *reinterpret_cast<const f4*>(xim + 4 * qc);
     const f4 sv = *reinterpret_cast<const f4*>(sim + 4 * qc);
     const f4 tv = *reinterpret_cast<const f4*>(tim0 + prc * nw + 4 * qc);
-    float xe[4], se[4];
-    gt_lane<OBJ>(ax.x, as.x, xv.x, sv.x, tv.x, dw.x, self, e.neg_lr, xe[0], se[0]);
-    gt_lane<OBJ>(ax.y, as.y, xv.y, sv.y, tv.y, dw.y, self, e.neg_lr, xe[1], se[1]);
-    gt_lane<OBJ>(ax.z, as.z, xv.z, sv.z, tv.z, dw.z, self, e.neg_lr, xe[2], se[2]);
-    gt_lane<OBJ>(ax.w, as.w, xv.w, sv.w, tv.w, dw.w, self, e.neg_lr, xe[3], se[3]);
-    const f4 xo{xe[0], xe[1], xe[2], xe[3]}, so{se[0], se[1], se[2], se[3]};
+    f4 xo, so;
+    gt_finish<OBJ>(ax, as, xv, sv, tv, dw, self, e.neg_lr, xo, so);
     const uint32_t offx = static_cast<uint32_t>((pr * e.ldxo + 4 * q) * 4);
     const uint32_t offs = static_cast<uint32_t>((pr * e.ldso + 4 * q) * 4);
     if (4 * q + 3 < n_rows || q >= nq) {  // whole quad, or none (dropped)
@@ -557,15 +541,15 @@ __device__ __forceinline__ void gt_stage(const Quad (&Q)[1], f4 dw, const float*
     } else {  // the ragged last quad (elements named one by one: hipcc 7.2 stored
               // element 0 four times from a loop over y[a] here)
       const int left = n_rows - 4 * q;  // 1..3
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[0]), rx, prow_ok ? offx : kOOB, 0, kNT);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[1]), rx, prow_ok && left > 1 ? offx + 4 : kOOB, 0,
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.x), rx, prow_ok ? offx : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.y), rx, prow_ok && left > 1 ? offx + 4 : kOOB, 0,
                                             kNT);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xe[2]), rx, prow_ok && left > 2 ? offx + 8 : kOOB, 0,
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.z), rx, prow_ok && left > 2 ? offx + 8 : kOOB, 0,
                                             kNT);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[0]), rs, prow_ok ? offs : kOOB, 0, kNT);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[1]), rs, prow_ok && left > 1 ? offs + 4 : kOOB, 0,
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(so.x), rs, prow_ok ? offs : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(so.y), rs, prow_ok && left > 1 ? offs + 4 : kOOB, 0,
                                             kNT);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(se[2]), rs, prow_ok && left > 2 ? offs + 8 : kOOB, 0,
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(so.z), rs, prow_ok && left > 2 ? offs + 8 : kOOB, 0,
                                             kNT);
     }
   }
@@ -844,7 +828,9 @@ constexpr int kGtMaxAgents = 4 * kT1;  // one quad per thread
 
 // The gradient-tracking round: validation in mix_csr_pm_impl's order, then
 // csr_pm_gt_kernel in the small geometry (1024-thread workgroups, one per CU,
-// one quad per thread).
+// one quad per thread).  It keeps its own validation rather than GtRows
+// (dol_launch.h): the objective comes first here, the leading dimensions cover
+// agents not P, alignment is required, and the messages name XT, ST and TT.
 int gt_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, const float* ST, int64_t ld_s, float* XO,
                    int64_t ldxo, float* SO, int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr,
                    const int32_t* col, const float* val, const float* self_w, const float* TT, int64_t ldt,

@@ -17,12 +17,12 @@ biased fixed point; the mix inside this round is its consensus
 (DIST/clients.py:61-69) in mix_csr_pm's rounding.  The argument rules are the
 validators of ops.py (_check_rows, _check_csr, _check_array) and pm_steps'
 square-W check, plus the four stated here: a known objective, at most
-ops.GT_MAX_AGENTS agents, four distinct state matrices and a self-weight
-vector of n floats; tests/test_gt_host.py pins them without a launch.
-gt_ring's own rules are in its docstring and in tests/test_gt_ring_host.py,
-gt_csr's in its docstring and in tests/test_gt_csr_host.py (those a CPU tensor
-reaches) and tests/test_gt_csr_gpu.py (the rest, with the library call
-recorded).
+ops.GT_MAX_AGENTS agents (gt_csr_pm), four distinct state matrices
+(_distinct_state) and weight vectors of n floats; tests/test_gt_host.py pins
+them for the three ops without a launch.  gt_ring's own rules are in its
+docstring and in tests/test_gt_ring_host.py, gt_csr's in its docstring and in
+tests/test_gt_csr_gpu.py (the ones a CPU tensor does not reach, with the
+library call recorded).
 """
 from __future__ import annotations
 
@@ -39,6 +39,23 @@ def _check_objective(name: str, objective: str) -> int:
     if objective not in _ops.OBJECTIVES:
         raise ValueError(f"{name}: objective must be one of {sorted(_ops.OBJECTIVES)}")
     return _ops.OBJECTIVES[objective]
+
+
+def _distinct_state(name: str, state) -> None:
+    """state: the four (name, matrix) pairs a round reads and writes."""
+    for i, (na, a) in enumerate(state):
+        for nb, b in state[i + 1:]:
+            if a is b or a.data_ptr() == b.data_ptr():
+                raise ValueError(f"{name}: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+
+
+def _leading_dims(state, target, P: int, n: int, pmajor: bool = False):
+    """The leading dimensions of the four state matrices and the targets ((name,
+    matrix) pairs) on the first one's device: [>= n, >= P] row matrices on the
+    agent-major bank, [>= P, >= n] on the parameter-major one."""
+    cols, rows, want, width = (None, P, f"[>= {P}, >= {n}]", n) if pmajor else (P, n, f">= {n} rows", 0)
+    return tuple(_ops._check_rows(nm, t, cols, rows, f"{nm}: expected {want} on {{}}", width, state[0][1].device)
+                 for nm, t in state + (target,))
 
 
 def gt_csr_pm(XT: torch.Tensor, ST: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, rowptr: torch.Tensor,
@@ -61,16 +78,11 @@ def gt_csr_pm(XT: torch.Tensor, ST: torch.Tensor, XO: torch.Tensor, SO: torch.Te
     if n > _ops.GT_MAX_AGENTS:
         raise ValueError(f"gt_csr_pm: the gradient-tracking round takes at most {_ops.GT_MAX_AGENTS} agents (got {n})")
     state = (("XT", XT), ("ST", ST), ("XO", XO), ("SO", SO))
-    for i, (na, a) in enumerate(state):
-        for nb, b in state[i + 1:]:
-            if a is b or a.data_ptr() == b.data_ptr():
-                raise ValueError(f"gt_csr_pm: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+    _distinct_state("gt_csr_pm", state)
     if self_weight is not None:
         _ops._check_array("self_weight", self_weight, torch.float32, n, XT.device)
     P = XT.shape[0] if P is None else P
-    ldx, ld_s, ldxo, ldso, ldt = (
-        _ops._check_rows(nm, t, None, P, f"{nm}: expected [>= {P}, >= {n}] on {{}}", n, XT.device)
-        for nm, t in state + (("TT", TT),))
+    ldx, ld_s, ldxo, ldso, ldt = _leading_dims(state, ("TT", TT), P, n, pmajor=True)
     _ops._check_csr(rowptr, col, val, XT.device, same_length=False)
     _check_square(rowptr, col, n)
     if nseg is None:
@@ -103,10 +115,7 @@ def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor
     P = X.shape[1] if P is None else P
     n = X.shape[0] if n_rows is None else n_rows
     state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
-    for i, (na, a) in enumerate(state):
-        for nb, b in state[i + 1:]:
-            if a is b or a.data_ptr() == b.data_ptr():
-                raise ValueError(f"gt_ring: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+    _distinct_state("gt_ring", state)
     for nm, w in (("w_prev", w_prev), ("w_next", w_next)) + ((("self_weight", self_weight),) if self_weight is not None
                                                               else ()):
         _ops._check_array(nm, w, torch.float32, n, X.device)
@@ -115,9 +124,7 @@ def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor
             raise ValueError("gt_ring: halos are (x_prev, x_next, s_prev, s_next), all four or None")
     elif n < 3:
         raise ValueError("gt_ring: a wrap-around ring needs >= 3 rows (pass halos, or use gt_csr_pm)")
-    ldx, ld_s, ldxo, ldso, ldt = (
-        _ops._check_rows(nm, t, P, n, f"{nm}: expected >= {n} rows on {{}}", 0, X.device)
-        for nm, t in state + (("target", target),))
+    ldx, ld_s, ldxo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
     for nm, h in zip(("x_prev", "x_next", "s_prev", "s_next"), halos or ()):
         _ops._check_vec(f"halos {nm}", h, P, X.device)
     hp = [None] * 4 if halos is None else [h.data_ptr() for h in halos]
@@ -146,16 +153,11 @@ def gt_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor,
     obj = _check_objective("gt_csr", objective)
     n = rowptr.shape[0] - 1
     state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
-    for i, (na, a) in enumerate(state):
-        for nb, b in state[i + 1:]:
-            if a is b or a.data_ptr() == b.data_ptr():
-                raise ValueError(f"gt_csr: {na} and {nb} alias: the Jacobi update of x and s needs four buffers")
+    _distinct_state("gt_csr", state)
     if self_weight is not None:
         _ops._check_array("self_weight", self_weight, torch.float32, n, X.device)
     P = X.shape[1] if P is None else P
-    ldx, ld_s, ldxo, ldso, ldt = (
-        _ops._check_rows(nm, t, P, n, f"{nm}: expected >= {n} rows on {{}}", 0, X.device)
-        for nm, t in state + (("target", target),))
+    ldx, ld_s, ldxo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
     _ops._check_csr(rowptr, col, val, X.device, same_length=False)
     _check_square(rowptr, col, n)
     _native.call("dol_gt_csr_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,

@@ -27,6 +27,40 @@ from .bank import AgentBank
 from .graph import MixingPlan
 
 
+def _seeded_draw(x: torch.Tensor, t: torch.Tensor, objective: str, seed: int, dev) -> None:
+    """The seeded init of every config-3 problem, from one generator on dev in
+    this order: x standard normal, t standard normal, and for the logistic loss
+    a random sign on t (t = label (+-1) * feature)."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    x.normal_(generator=g)
+    t.normal_(generator=g)
+    if objective == "logistic":
+        t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+
+
+def _gt_rules(objective: str, self_weight, n: int, dev) -> Optional[torch.Tensor]:
+    """The rules of both gradient-tracking problems: a known objective, and n
+    self weights (or None), returned as a contiguous float32 vector on dev."""
+    from . import ops
+    if objective not in ops.OBJECTIVES:
+        raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
+    if self_weight is None:
+        return None
+    w = torch.as_tensor(self_weight, dtype=torch.float32).to(dev).contiguous()
+    if w.shape != (n,):
+        raise ValueError(f"self_weight: expected {n} weights")
+    return w
+
+
+def _distance_to_mean_target(x: torch.Tensor, t: torch.Tensor, agent_axis: int, objective: str) -> float:
+    """max over agents and coordinates of |x_ip - mean_j t_jp| (the mean in
+    fp64, over the agent axis): least squares only, whose optimum is the mean of
+    the targets."""
+    if objective != "least_squares":
+        raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
+    return float((x.double() - t.double().mean(agent_axis, keepdim=True)).abs().max())
+
+
 class SeparableDGD:
     def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
                  momentum: float = 0.0, local_steps: int = 1, seed: int = 2028, device=None,
@@ -37,12 +71,7 @@ class SeparableDGD:
         dev = plan.device if device is None else torch.device(device)
         self.bank = bank if bank is not None else AgentBank(plan.n_rows, P, dev)
         self.P = self.bank.P
-        g = torch.Generator(device=dev).manual_seed(seed)
-        self.bank.buffer("x").normal_(generator=g)
-        t = self.bank.buffer("target")
-        t.normal_(generator=g)
-        if objective == "logistic":  # t = label (+-1) * feature
-            t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+        _seeded_draw(self.bank.buffer("x"), self.bank.buffer("target"), objective, seed, dev)
         self.bank.buffer("y")
         if self.mu != 0.0:
             self.bank.buffer("mom", zero=True)
@@ -579,12 +608,7 @@ class SeparableDGDPM:
         self.MT = torch.zeros_like(self.XT) if self.mu != 0.0 else None
         self.first, self.rounds = True, 0
         if _state is None:
-            g = torch.Generator(device=dev).manual_seed(seed)
-            self.XT[:, :self.N].normal_(generator=g)
-            self.TT[:, :self.N].normal_(generator=g)
-            if objective == "logistic":
-                t = self.TT[:, :self.N]
-                t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+            _seeded_draw(self.XT[:, :self.N], self.TT[:, :self.N], objective, seed, dev)
 
     @classmethod
     def from_agent_major(cls, prob: "SeparableDGD", consensus_steps: int = 1) -> "SeparableDGDPM":
@@ -672,25 +696,14 @@ class SeparableGTPM:
             raise ValueError(f"the gradient-tracking round takes at most {ops.GT_MAX_AGENTS} agents")
         if plan.kind == "dense":
             raise ValueError("the gradient-tracking round mixes a sparse (CSR) W")
-        if objective not in ops.OBJECTIVES:
-            raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
         self.plan, self.P, self.objective, self.lr = plan, int(P), objective, float(lr)
         self.N = plan.n_rows
         self.ld = (self.N + 3) // 4 * 4
         dev = plan.device
-        self.self_weight = None
-        if self_weight is not None:
-            self.self_weight = torch.as_tensor(self_weight, dtype=torch.float32).to(dev).contiguous()
-            if self.self_weight.shape != (self.N,):
-                raise ValueError(f"self_weight: expected {self.N} weights")
+        self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
         self.XT = torch.zeros((self.P, self.ld), dtype=torch.float32, device=dev)
         self.XO, self.ST, self.SO, self.TT = (torch.zeros_like(self.XT) for _ in range(4))
-        g = torch.Generator(device=dev).manual_seed(seed)
-        self.XT[:, :self.N].normal_(generator=g)
-        self.TT[:, :self.N].normal_(generator=g)
-        if objective == "logistic":
-            t = self.TT[:, :self.N]
-            t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+        _seeded_draw(self.XT[:, :self.N], self.TT[:, :self.N], objective, seed, dev)
         ops.separable_grad(self.XT, self.TT, self.ST, objective)
         self.rounds = 0
 
@@ -729,12 +742,8 @@ class SeparableGTPM:
         return float((x - x.mean(1, keepdim=True)).norm() / max(1, self.N) ** 0.5)
 
     def distance_to_optimum(self) -> float:
-        """max over agents and coordinates of |x_ip - mean_j t_jp| (the mean in
-        fp64): least squares only, whose optimum is the mean of the targets."""
-        if self.objective != "least_squares":
-            raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
-        opt = self.TT[:, :self.N].double().mean(1, keepdim=True)
-        return float((self.XT[:, :self.N].double() - opt).abs().max())
+        """_distance_to_mean_target of the parameters (agents along axis 1)."""
+        return _distance_to_mean_target(self.XT[:, :self.N], self.TT[:, :self.N], 1, self.objective)
 
 
 def ring_gt_weights(ring_csr):
@@ -776,24 +785,13 @@ class SeparableGTCSR:
                  self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
         from . import ops
         self._check_plan(plan)
-        if objective not in ops.OBJECTIVES:
-            raise ValueError(f"objective must be one of {sorted(ops.OBJECTIVES)}")
         self.plan, self.objective, self.lr = plan, objective, float(lr)
         self.N = plan.n_rows
         dev = plan.device
-        self.self_weight = None
-        if self_weight is not None:
-            self.self_weight = torch.as_tensor(self_weight, dtype=torch.float32).to(dev).contiguous()
-            if self.self_weight.shape != (self.N,):
-                raise ValueError(f"self_weight: expected {self.N} weights")
+        self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
         self.bank = bank if bank is not None else AgentBank(self.N, P, dev)
         self.P = self.bank.P
-        g = torch.Generator(device=dev).manual_seed(seed)
-        self.bank.buffer("x").normal_(generator=g)
-        t = self.bank.buffer("target")
-        t.normal_(generator=g)
-        if objective == "logistic":  # t = label (+-1) * feature
-            t.copy_(torch.where(torch.rand(t.shape, generator=g, device=dev) < 0.5, -t, t))
+        _seeded_draw(self.bank.buffer("x"), self.bank.buffer("target"), objective, seed, dev)
         for name in ("y", "s", "s_out"):
             self.bank.buffer(name, zero=True)
         ops.separable_grad(self.bank.rows("x"), self.bank.rows("target"), self.bank.rows("s"), objective)
@@ -827,12 +825,8 @@ class SeparableGTCSR:
         return float((x - x.mean(0, keepdim=True)).norm() / max(1, x.shape[0]) ** 0.5)
 
     def distance_to_optimum(self) -> float:
-        """max over agents and coordinates of |x_ip - mean_j t_jp| (the mean in
-        fp64): least squares only, whose optimum is the mean of the targets."""
-        if self.objective != "least_squares":
-            raise ValueError("distance_to_optimum: the optimum is known in closed form for least squares only")
-        opt = self.targets().double().mean(0, keepdim=True)
-        return float((self.params().double() - opt).abs().max())
+        """_distance_to_mean_target of the parameters (agents along axis 0)."""
+        return _distance_to_mean_target(self.params(), self.targets(), 0, self.objective)
 
 
 class SeparableGT(SeparableGTCSR):

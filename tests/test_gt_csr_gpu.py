@@ -38,44 +38,17 @@ import pytest
 import torch
 
 import gt_cases
+from gt_cases import am, csr_dev, logistic_problem, padded, pm, problem, regular, same_bits
 from oracle import bits_equal
 from dolhip import graph as G
 from dolhip import ops, parallel
 from dolhip.synthetic import SeparableDGD, SeparableGT, SeparableGTCSR, SeparableGTPM
-from test_ops_args_gpu import Recorder, mat, named, vec
+from test_ops_args_gpu import mat, named, vec
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 I32 = torch.int32
-
-
-def same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-@functools.lru_cache(maxsize=None)
-def regular(n):
-    """(a random 4-regular W with its own 'stochastic' values, a self-weight vector)"""
-    return G.random_regular_csr(n, 4, seed=n + 3), np.linspace(0.05, 0.45, n).astype(F32)
-
-
-def csr_dev(c, gpu):
-    return tuple(torch.as_tensor(np.asarray(a, t), device=gpu) for a, t in
-                 ((c.rowptr, np.int32), (c.col, np.int32), (c.val, np.float32)))
-
-
-def problem(n, P, seed):
-    rng = np.random.default_rng(seed)
-    return tuple(rng.standard_normal((n, P)).astype(F32) for _ in range(3))
-
-
-def padded(A, ld, gpu, fill=float("nan"), off=0):
-    """Device copy of host A [n, P] in a [n, ld] matrix, `fill` in the padding
-    columns; off: the view starts `off` floats into each row."""
-    t = torch.full((A.shape[0], ld), fill, dtype=torch.float32, device=gpu)
-    t[:, off:off + A.shape[1]] = torch.as_tensor(A, device=gpu)
-    return t
 
 
 def run_csr(X, S, T, c, ws, gpu, objective="least_squares", lr=0.1, ld=None, off=0):
@@ -265,20 +238,12 @@ def test_nonfinite_and_signed_zero_inputs(n, P, self_w, gpu):
 # ---------------------------------------------------------------------------
 # the siblings' bits
 # ---------------------------------------------------------------------------
-def logistic_problem(n, P):
-    rng = np.random.default_rng(n + P)
-    X, S, T = problem(n, P, n + 31)
-    return X, S, np.where(rng.random(T.shape) < 0.5, -T, T).astype(F32)  # targets +-feature
-
-
 @pytest.mark.parametrize("self_w", [False, True], ids=["no self weights", "self weights"])
 @pytest.mark.parametrize("objective", ["least_squares", "logistic"])
 @pytest.mark.parametrize("n", [9, 64, 520])
 def test_same_bits_as_the_ring_round_on_a_ring_csr(n, objective, self_w, gpu):
-    torch.manual_seed(2028 + n)
-    c = G.communication_csr("circle", "stochastic", n)[0]
-    wp, wn = c.ring_weights()
-    d = np.linspace(0.05, 0.45, n).astype(F32) if self_w else None
+    c, wp, wn, d = gt_cases.ring(n)
+    d = d if self_w else None
     P = 1031
     X, S, T = logistic_problem(n, P)
     got_x, got_s = run_csr(X, S, T, c, d, gpu, objective=objective)
@@ -288,14 +253,6 @@ def test_same_bits_as_the_ring_round_on_a_ring_csr(n, objective, self_w, gpu):
                 self_weight=None if d is None else torch.as_tensor(d, device=gpu), objective=objective, lr=0.1, P=P)
     torch.cuda.synchronize()
     assert bits_equal(got_x, XO[:, :P].cpu().numpy()) and bits_equal(got_s, SO[:, :P].cpu().numpy())
-
-
-def pm(A, gpu):
-    """Parameter-major device copy [P, round_up(n, 4)] of agent-major host A [n, P]."""
-    n, P = A.shape
-    t = torch.zeros((P, (n + 3) // 4 * 4), dtype=torch.float32, device=gpu)
-    t[:, :n] = torch.as_tensor(np.ascontiguousarray(A.T), device=gpu)
-    return t
 
 
 @pytest.mark.parametrize("objective", ["least_squares", "logistic"])
@@ -310,33 +267,26 @@ def test_same_bits_as_the_parameter_major_round(n, objective, gpu):
     ops.gt_csr_pm(XT, ST, XO, SO, *csr_dev(c, gpu), TT, self_weight=torch.as_tensor(d, device=gpu),
                   objective=objective, lr=0.1)
     torch.cuda.synchronize()
-    assert bits_equal(got_x, np.ascontiguousarray(XO[:, :n].cpu().numpy().T))
-    assert bits_equal(got_s, np.ascontiguousarray(SO[:, :n].cpu().numpy().T))
+    assert bits_equal(got_x, am(XO, n))
+    assert bits_equal(got_s, am(SO, n))
 
 
 @pytest.mark.parametrize("self_w", [False, True], ids=["no self weights", "self weights"])
 def test_logistic_vs_device_composition_beyond_the_cap(self_w, gpu):
-    """4100 x 132, where neither sibling runs: ax, as from ops.mix_csr; the
-    self-weight terms and x' on the host (gt_cases: one rounding each, an exact
-    fma); g(x') and g(x) from ops.separable_grad; s' from two separate fp32
-    torch ops."""
+    """4100 x 132, where neither sibling runs: gt_cases.logistic_round with ax,
+    as from ops.mix_csr."""
     n, P = 4100, 132
     c, d = regular(n)
     d = d if self_w else None
     X, S, T = logistic_problem(n, P)
     got_x, got_s = run_csr(X, S, T, c, d, gpu, objective="logistic")
     rp, col, val = csr_dev(c, gpu)
-    mixes = []
-    for A in (X, S):
+
+    def mix(A):
         Y = torch.empty(n, P, device=gpu)
         ops.mix_csr(torch.as_tensor(A, device=gpu), Y, rp, col, val)
-        mixes.append(gt_cases.add_self(Y.cpu().numpy(), d, A))
-    ax, as_ = mixes
-    want_x = gt_cases.sgd_step(ax, S, 0.1)
-    Td = torch.as_tensor(T, device=gpu)
-    g1 = ops.separable_grad(torch.as_tensor(want_x, device=gpu), Td, None, "logistic")
-    g0 = ops.separable_grad(torch.as_tensor(X, device=gpu), Td, None, "logistic")
-    want_s = torch.sub(torch.add(torch.as_tensor(as_, device=gpu), g1), g0).cpu().numpy()
+        return Y.cpu().numpy()
+    want_x, want_s = gt_cases.logistic_round(mix, X, S, T, d, gpu)
     assert bits_equal(got_x, want_x)
     assert bits_equal(got_s, want_s)
 
@@ -394,19 +344,17 @@ def test_apply_gt_with_a_slab_pack_runs_gt_csr_and_dense_raises(gpu, monkeypatch
 # ---------------------------------------------------------------------------
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    monkeypatch.setattr(ops._native, "call", r)
-    return r
+    return gt_cases.recorder(monkeypatch)
 
 
-def _args(dev, n=4, P=10, ld=12):
-    return dict(X=mat(dev, n, P, ld), S=mat(dev, n, P, ld), XO=mat(dev, n, P, ld), SO=mat(dev, n, P, ld),
-                rowptr=torch.tensor([0, 1, 2, 3, 4], dtype=I32, device=dev)[:n + 1],
-                col=torch.tensor([1, 0, 3, 2], dtype=I32, device=dev), val=vec(dev, 4), target=mat(dev, n, P, ld))
+def _args(dev):
+    """gt_cases.host_args with a W that is square: the perfect matching 0 - 1, 2 - 3."""
+    return dict(gt_cases.host_args("gt_csr", dev), rowptr=torch.tensor([0, 1, 2, 3, 4], dtype=I32, device=dev),
+                col=torch.tensor([1, 0, 3, 2], dtype=I32, device=dev))
 
 
 def _call(t, **kw):
-    return ops.gt_csr(t["X"], t["S"], t["XO"], t["SO"], t["rowptr"], t["col"], t["val"], t["target"], **kw)
+    return gt_cases.host_call("gt_csr", t, **kw)
 
 
 def test_a_non_square_w_is_refused(gpu, rec):

@@ -6,11 +6,12 @@ is launched.
 * Every argument rule of the entry point, called through the library with
   addresses that are never dereferenced (each refusal returns before a launch
   and names the entry), and DOL_OK for the empty shapes.
-* The rules of ops.gt_csr that a CPU tensor can reach, MixingPlan.apply_gt's
-  routing by kind and SeparableGTCSR's refusals, with ops._native.call replaced
-  by test_ops_args_gpu.Recorder.  (A CPU matrix is refused before the square-W
-  and row-count rules are looked at; those and the accepted call's argument
-  tuple are pinned with the Recorder on device tensors in
+* MixingPlan.apply_gt's routing by kind and SeparableGTCSR's refusals, with
+  ops._native.call replaced by test_ops_args_gpu.Recorder.  (The rules of
+  ops.gt_csr that a CPU tensor can reach are the ones it shares with
+  ops.gt_csr_pm and ops.gt_ring: tests/test_gt_host.py.  A CPU matrix is refused
+  before the square-W and row-count rules are looked at; those and the accepted
+  call's argument tuple are pinned with the Recorder on device tensors in
   tests/test_gt_csr_gpu.py.)
 * ColumnSharded.gt_step with tests/gt_cases.py::gt_round injected as the
   arithmetic: world 1 in-process, worlds 2 and 3 over gloo; the gathered
@@ -47,11 +48,10 @@ import gt_cases
 import oracle
 from dolhip import _native, graph as G, gt, ops, parallel
 from dolhip.bank import row_stride
-from dolhip.ops import DolNativeError
 from dolhip.synthetic import SeparableGT, SeparableGTCSR
 from test_codegen_pins import LLVM, _kernels, _unbundle
 from test_kernel_extents import KT, Ext, cdiv
-from test_ops_args_gpu import Recorder, mat, vec
+from test_ops_args_gpu import mat, vec
 
 CPU = torch.device("cpu")
 F32 = np.float32
@@ -115,52 +115,7 @@ def test_entry_point_checks_arguments_without_launch():
 # ---------------------------------------------------------------------------
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    monkeypatch.setattr(ops._native, "call", r)
-    return r
-
-
-def _args(dev, n=4, P=10, ld=12):
-    return dict(X=mat(dev, n, P, ld), S=mat(dev, n, P, ld), XO=mat(dev, n, P, ld), SO=mat(dev, n, P, ld),
-                rowptr=vec(dev, n + 1, I32), col=vec(dev, 4, I32), val=vec(dev, 4), target=mat(dev, n, P, ld))
-
-
-def _call(t, **kw):
-    return ops.gt_csr(t["X"], t["S"], t["XO"], t["SO"], t["rowptr"], t["col"], t["val"], t["target"], **kw)
-
-
-def test_unknown_objective_is_refused(rec):
-    with pytest.raises(ValueError, match="gt_csr: objective must be one of"):
-        _call(_args(CPU), objective="hinge")
-    assert rec.calls == []
-
-
-@pytest.mark.parametrize("a,b", [("X", "S"), ("X", "XO"), ("X", "SO"), ("S", "XO"), ("S", "SO"), ("XO", "SO")])
-def test_two_state_matrices_the_same_tensor_are_refused(a, b, rec):
-    t = _args(CPU)
-    t[b] = t[a]
-    with pytest.raises(ValueError, match=f"gt_csr: {a} and {b} alias"):
-        _call(t)
-    t = _args(CPU)
-    t[b] = t[a][:, :10]  # another view of the same rows
-    with pytest.raises(ValueError, match=f"gt_csr: {a} and {b} alias"):
-        _call(t)
-    assert rec.calls == []
-
-
-@pytest.mark.parametrize("bad", [lambda: vec(CPU, 3), lambda: vec(CPU, 4, torch.float64),
-                                 lambda: torch.zeros(4, device="meta"), lambda: vec(CPU, 8)[::2]],
-                         ids=["length", "dtype", "device", "stride"])
-def test_bad_self_weight_is_refused(bad, rec):
-    with pytest.raises(ValueError, match=r"self_weight: expected contiguous float32 \[4\] on cpu"):
-        _call(_args(CPU), self_weight=bad())
-    assert rec.calls == []
-
-
-def test_cpu_tensors_are_refused(rec):
-    with pytest.raises(DolNativeError, match="cpu"):
-        _call(_args(CPU), self_weight=vec(CPU, 4), objective="logistic", lr=0.5, P=10)
-    assert rec.calls == []
+    return gt_cases.recorder(monkeypatch)
 
 
 def _ring_pattern(n):
@@ -174,7 +129,7 @@ def test_apply_gt_routes_by_kind(monkeypatch, rec):
     monkeypatch.setattr(ops, "gt_csr", lambda *a, **k: seen.append(("gt_csr", a, k)) or (a[2], a[3]))
     monkeypatch.setattr(ops, "mix_csr_slab", lambda *a, **k: seen.append(("slab", a, k)))
     c9 = _ring_pattern(9)
-    t = _args(CPU, n=9)
+    t = gt_cases.host_args("gt_csr", CPU, n=9)
     d = vec(CPU, 9)
     kw = dict(self_weight=d, objective="logistic", lr=0.5, P=10)
     five = (t["X"], t["S"], t["XO"], t["SO"])

@@ -1,7 +1,12 @@
 """Gradient tracking on the parameter-major bank, CPU tier (launch-free:
 ops._native.call is replaced by test_ops_args_gpu.Recorder where an op is
-called).
+called), and the rules the three ops share.
 
+* The rules that ops.gt_csr_pm, ops.gt_ring and ops.gt_csr state alike, each
+  tested once over the three (gt_cases.ENTRIES): an unknown objective, each
+  pair of the four state matrices aliased, bad weight vectors, CPU tensors.
+  The rules of one layout are in tests/test_gt_ring_host.py and
+  tests/test_gt_csr_host.py.
 * The surface: ops re-exports, ops.GT_MAX_AGENTS, the three SIGNATURES rows.
 * Every refusal of ops.gt_csr_pm / ops.separable_grad / SeparableGTPM comes
   before the library is reached, and the entry points themselves refuse bad
@@ -24,28 +29,27 @@ import torch
 import gt_cases
 from dolhip import _native, graph as G, gt, ops
 from dolhip.ops import DolNativeError
-from test_ops_args_gpu import Recorder, mat, vec
+from test_ops_args_gpu import vec
 
 CPU = torch.device("cpu")
 I32 = torch.int32
 F32 = np.float32
 
 
+OPS = sorted(gt_cases.ENTRIES)
+
+
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    monkeypatch.setattr(ops._native, "call", r)
-    return r
+    return gt_cases.recorder(monkeypatch)
 
 
-def _args(dev, n=2, P=10):
-    ld = (n + 3) // 4 * 4
-    return dict(XT=mat(dev, P, n, ld), ST=mat(dev, P, n, ld), XO=mat(dev, P, n, ld), SO=mat(dev, P, n, ld),
-                rowptr=vec(dev, n + 1, I32), col=vec(dev, 4, I32), val=vec(dev, 4), TT=mat(dev, P, n, ld))
+def _args(dev):
+    return gt_cases.host_args("gt_csr_pm", dev)
 
 
 def _call(t, **kw):
-    return ops.gt_csr_pm(t["XT"], t["ST"], t["XO"], t["SO"], t["rowptr"], t["col"], t["val"], t["TT"], **kw)
+    return gt_cases.host_call("gt_csr_pm", t, **kw)
 
 
 # ---------------------------------------------------------------------------
@@ -75,39 +79,55 @@ def test_more_than_4096_agents_are_refused(rec):
     assert rec.calls == []
 
 
-@pytest.mark.parametrize("a,b", [("XT", "ST"), ("XT", "XO"), ("XT", "SO"), ("ST", "XO"), ("ST", "SO"), ("XO", "SO")])
-def test_two_state_matrices_the_same_tensor_are_refused(a, b, rec):
-    t = _args(CPU)
+@pytest.mark.parametrize("op", OPS)
+def test_unknown_objective_is_refused(op, rec):
+    t = gt_cases.host_args(op, CPU)
+    with pytest.raises(ValueError, match=f"{op}: objective must be one of"):
+        gt_cases.host_call(op, t, objective="hinge")
+    if op == "gt_csr_pm":
+        with pytest.raises(ValueError, match="objective must be one of"):
+            ops.separable_grad(t["XT"], t["TT"], t["XO"], "hinge")
+    assert rec.calls == []
+
+
+@pytest.mark.parametrize("op,a,b", [(op, e["state"][i], e["state"][j]) for op, e in sorted(gt_cases.ENTRIES.items())
+                                    for i in range(4) for j in range(i + 1, 4)])
+def test_two_state_matrices_the_same_tensor_are_refused(op, a, b, rec):
+    t = gt_cases.host_args(op, CPU)
     t[b] = t[a]
-    with pytest.raises(ValueError, match=f"{a} and {b} alias"):
-        _call(t)
+    with pytest.raises(ValueError, match=f"{op}: {a} and {b} alias"):
+        gt_cases.host_call(op, t)
+    t = gt_cases.host_args(op, CPU)
+    t[b] = t[a][:, :t[a].shape[1]]  # another view of the same rows
+    with pytest.raises(ValueError, match=f"{op}: {a} and {b} alias"):
+        gt_cases.host_call(op, t)
     assert rec.calls == []
 
 
-def test_unknown_objective_is_refused(rec):
-    t = _args(CPU)
-    with pytest.raises(ValueError, match="objective must be one of"):
-        _call(t, objective="hinge")
-    with pytest.raises(ValueError, match="objective must be one of"):
-        ops.separable_grad(t["XT"], t["TT"], t["XO"], "hinge")
-    assert rec.calls == []
-
-
-@pytest.mark.parametrize("sw", [lambda: vec(CPU, 1), lambda: vec(CPU, 2, torch.float64),
-                                lambda: torch.zeros(2, device="meta"), lambda: vec(CPU, 4)[::2]],
+@pytest.mark.parametrize("op,name", [(op, v) for op, e in sorted(gt_cases.ENTRIES.items()) for v in e["vectors"]])
+@pytest.mark.parametrize("bad", [lambda n: vec(CPU, n - 1), lambda n: vec(CPU, n, torch.float64),
+                                 lambda n: torch.zeros(n, device="meta"), lambda n: vec(CPU, 2 * n)[::2]],
                          ids=["length", "dtype", "device", "stride"])
-def test_bad_self_weight_is_refused(sw, rec):
-    with pytest.raises(ValueError, match=r"self_weight: expected contiguous float32 \[2\] on cpu"):
-        _call(_args(CPU), self_weight=sw())
+def test_bad_weight_vectors_are_refused(op, name, bad, rec):
+    n = gt_cases.ENTRIES[op]["n"]
+    t, kw = gt_cases.host_args(op, CPU), {}
+    if name == "self_weight":
+        kw[name] = bad(n)
+    else:
+        t[name] = bad(n)
+    with pytest.raises(ValueError, match=rf"{name}: expected contiguous float32 \[{n}\] on cpu"):
+        gt_cases.host_call(op, t, **kw)
     assert rec.calls == []
 
 
-def test_cpu_tensors_are_refused(rec):
-    t = _args(CPU)
+@pytest.mark.parametrize("op", OPS)
+def test_cpu_tensors_are_refused(op, rec):
+    t, n = gt_cases.host_args(op, CPU), gt_cases.ENTRIES[op]["n"]
     with pytest.raises(DolNativeError, match="cpu"):
-        _call(t, self_weight=vec(CPU, 2), objective="logistic", lr=0.5, P=10, nseg=8)
-    with pytest.raises(DolNativeError, match="cpu"):
-        ops.separable_grad(t["XT"], t["TT"], t["XO"], "logistic")
+        gt_cases.host_call(op, t, self_weight=vec(CPU, n), objective="logistic", lr=0.5, **gt_cases.ENTRIES[op]["kw"])
+    if op == "gt_csr_pm":
+        with pytest.raises(DolNativeError, match="cpu"):
+            ops.separable_grad(t["XT"], t["TT"], t["XO"], "logistic")
     assert rec.calls == []
 
 

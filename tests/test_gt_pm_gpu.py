@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import gt_cases
+from gt_cases import am, csr_dev, pm, problem, same_bits
 from oracle import bits_equal
 from dolhip import graph as G
 from dolhip import ops
@@ -29,29 +30,6 @@ from test_dgd_gpu import LOGISTIC_TOL
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-
-
-def csr_dev(c, gpu):
-    return (torch.as_tensor(np.asarray(c.rowptr, np.int32), device=gpu),
-            torch.as_tensor(np.asarray(c.col, np.int32), device=gpu),
-            torch.as_tensor(np.asarray(c.val, np.float32), device=gpu))
-
-
-def pm(X, gpu, extra=0):
-    """Parameter-major device copy of agent-major X [n, P]: [P, round_up(n, 4) + extra], NaN padding."""
-    n, P = X.shape
-    t = torch.full((P, (n + 3) // 4 * 4 + extra), float("nan"), dtype=torch.float32, device=gpu)
-    t[:, :n] = torch.as_tensor(np.ascontiguousarray(X.T), device=gpu)
-    return t
-
-
-def am(t, n):
-    """Agent-major host copy [n, P] of a parameter-major device matrix."""
-    return np.ascontiguousarray(t[:, :n].cpu().numpy().T)
-
-
-def same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def run_gt(X, S, T, c, d, gpu, objective="least_squares", lr=0.1, extra=0, nseg=None):
@@ -71,12 +49,6 @@ def run_gt(X, S, T, c, d, gpu, objective="least_squares", lr=0.1, extra=0, nseg=
     for t, k in zip((XT, ST, TT), keep):
         assert same_bits(t, k), "an input changed"
     return am(XO, n), am(SO, n)
-
-
-def problem(n, P, seed):
-    rng = np.random.default_rng(seed)
-    X, S, T = (rng.standard_normal((n, P)).astype(F32) for _ in range(3))
-    return X, S, T
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,19 +123,10 @@ def test_long_rows_and_nonfinite(self_w, gpu):
     assert bits_equal(got_x, want_x) and bits_equal(got_s, want_s)
 
 
-def device_grad(gpu, objective):
-    """g(x, t) on agent-major host arrays through ops.separable_grad."""
-    def grad(x, t):
-        xd, td = (torch.as_tensor(np.ascontiguousarray(a, F32), device=gpu) for a in (x, t))
-        return ops.separable_grad(xd, td, None, objective).cpu().numpy()
-    return grad
-
-
 def _logistic_case(n, P, self_w, gpu, extra=0):
-    """The logistic round against the device composition: ax, as from
-    ops.mix_csr_pm; the self-weight terms and x' on the host (gt_cases); g(x')
-    and g(x) from ops.separable_grad; s' from two separate fp32 torch ops.
-    Targets +-feature, as SeparableDGDPM draws them."""
+    """The logistic round against the device composition
+    (gt_cases.logistic_round) with ax, as from ops.mix_csr_pm.  Targets
+    +-feature, as SeparableDGDPM draws them."""
     c, m, d = _regular(n)
     W, d = (m, d) if self_w else (c, None)
     rng = np.random.default_rng(n + P)
@@ -171,16 +134,12 @@ def _logistic_case(n, P, self_w, gpu, extra=0):
     T = np.where(rng.random(T.shape) < 0.5, -T, T).astype(F32)
     got_x, got_s = run_gt(X, S, T, W, d, gpu, objective="logistic", lr=0.1, extra=extra)
     rp, col, val = csr_dev(W, gpu)
-    mixes = []
-    for A in (X, S):
-        AT, YT = pm(A, gpu), torch.full((P, (n + 3) // 4 * 4), 7.0, device=gpu)
-        ops.mix_csr_pm(AT, YT, rp, col, val)
-        mixes.append(gt_cases.add_self(am(YT, n), d, A))
-    ax, as_ = mixes
-    want_x = gt_cases.sgd_step(ax, S, 0.1)
-    grad = device_grad(gpu, "logistic")
-    g1, g0, asd = (torch.as_tensor(a, device=gpu) for a in (grad(want_x, T), grad(X, T), as_))
-    want_s = torch.sub(torch.add(asd, g1), g0).cpu().numpy()
+
+    def mix(A):
+        YT = torch.full((P, (n + 3) // 4 * 4), 7.0, device=gpu)
+        ops.mix_csr_pm(pm(A, gpu), YT, rp, col, val)
+        return am(YT, n)
+    want_x, want_s = gt_cases.logistic_round(mix, X, S, T, d, gpu)
     assert bits_equal(got_x, want_x)
     assert bits_equal(got_s, want_s)
 

@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import gt_cases
+from gt_cases import am, csr_dev, logistic_problem, padded, pm, problem, ring, same_bits
 from oracle import bits_equal
 from dolhip import graph as G
 from dolhip import ops
@@ -32,31 +33,6 @@ from dolhip.synthetic import SeparableDGD, SeparableGT, SeparableGTPM, ring_gt_w
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
-
-
-def same_bits(a, b):
-    return torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-@functools.lru_cache(maxsize=None)
-def ring(n):
-    """(the reference's stochastic circle W as a CSR, its w_prev, w_next, a self-weight vector)"""
-    torch.manual_seed(2028 + n)
-    c = G.communication_csr("circle", "stochastic", n)[0]
-    wp, wn = c.ring_weights()
-    return c, wp, wn, np.linspace(0.05, 0.45, n).astype(F32)
-
-
-def problem(n, P, seed):
-    rng = np.random.default_rng(seed)
-    return tuple(rng.standard_normal((n, P)).astype(F32) for _ in range(3))
-
-
-def padded(A, ld, gpu, fill=float("nan")):
-    """Device copy of host A [n, P] in a [n, ld] matrix, `fill` in the padding columns."""
-    t = torch.full((A.shape[0], ld), fill, dtype=torch.float32, device=gpu)
-    t[:, :A.shape[1]] = torch.as_tensor(A, device=gpu)
-    return t
 
 
 def run_ring(X, S, T, wp, wn, ws, gpu, objective="least_squares", lr=0.1, ld=None, blocks=None):
@@ -198,20 +174,6 @@ def test_nonfinite_and_signed_zero_inputs(P, self_w, gpu):
 # ---------------------------------------------------------------------------
 # logistic: against the parameter-major round and against a device composition
 # ---------------------------------------------------------------------------
-def pm(A, gpu):
-    """Parameter-major device copy [P, round_up(n, 4)] of agent-major host A [n, P]."""
-    n, P = A.shape
-    t = torch.zeros((P, (n + 3) // 4 * 4), dtype=torch.float32, device=gpu)
-    t[:, :n] = torch.as_tensor(np.ascontiguousarray(A.T), device=gpu)
-    return t
-
-
-def logistic_problem(n, P):
-    rng = np.random.default_rng(n + P)
-    X, S, T = problem(n, P, n + 31)
-    return X, S, np.where(rng.random(T.shape) < 0.5, -T, T).astype(F32)  # targets +-feature
-
-
 @pytest.mark.parametrize("self_w", [False, True], ids=["no self weights", "self weights"])
 @pytest.mark.parametrize("objective", ["least_squares", "logistic"])
 @pytest.mark.parametrize("n", [9, 64])
@@ -223,37 +185,29 @@ def test_same_bits_as_the_parameter_major_round(n, objective, self_w, gpu):
     got_x, got_s = run_ring(X, S, T, wp, wn, d, gpu, objective=objective)
     XT, ST, TT = (pm(A, gpu) for A in (X, S, T))
     XO, SO = torch.zeros_like(XT), torch.zeros_like(XT)
-    ops.gt_csr_pm(XT, ST, XO, SO, *(torch.as_tensor(np.asarray(a, t), device=gpu) for a, t in
-                                    ((c.rowptr, np.int32), (c.col, np.int32), (c.val, np.float32))), TT,
+    ops.gt_csr_pm(XT, ST, XO, SO, *csr_dev(c, gpu), TT,
                   self_weight=None if d is None else torch.as_tensor(d, device=gpu), objective=objective, lr=0.1)
     torch.cuda.synchronize()
-    assert bits_equal(got_x, np.ascontiguousarray(XO[:, :n].cpu().numpy().T))
-    assert bits_equal(got_s, np.ascontiguousarray(SO[:, :n].cpu().numpy().T))
+    assert bits_equal(got_x, am(XO, n))
+    assert bits_equal(got_s, am(SO, n))
 
 
 @pytest.mark.parametrize("self_w", [False, True], ids=["no self weights", "self weights"])
 @pytest.mark.parametrize("n", [9, 64])
 def test_logistic_vs_device_composition(n, self_w, gpu):
-    """ax, as from ops.mix_ring; the self-weight terms and x' on the host
-    (gt_cases: one rounding each, an exact fma); g(x') and g(x) from
-    ops.separable_grad; s' from two separate fp32 torch ops."""
+    """gt_cases.logistic_round with ax, as from ops.mix_ring."""
     c, wp, wn, d = ring(n)
     d = d if self_w else None
     P = 1031
     X, S, T = logistic_problem(n, P)
     got_x, got_s = run_ring(X, S, T, wp, wn, d, gpu, objective="logistic")
     wpd, wnd = torch.as_tensor(wp, device=gpu), torch.as_tensor(wn, device=gpu)
-    mixes = []
-    for A in (X, S):
+
+    def mix(A):
         Y = torch.empty(n, P, device=gpu)
         ops.mix_ring(torch.as_tensor(A, device=gpu), Y, wpd, wnd)
-        mixes.append(gt_cases.add_self(Y.cpu().numpy(), d, A))
-    ax, as_ = mixes
-    want_x = gt_cases.sgd_step(ax, S, 0.1)
-    Td = torch.as_tensor(T, device=gpu)
-    g1 = ops.separable_grad(torch.as_tensor(want_x, device=gpu), Td, None, "logistic")
-    g0 = ops.separable_grad(torch.as_tensor(X, device=gpu), Td, None, "logistic")
-    want_s = torch.sub(torch.add(torch.as_tensor(as_, device=gpu), g1), g0).cpu().numpy()
+        return Y.cpu().numpy()
+    want_x, want_s = gt_cases.logistic_round(mix, X, S, T, d, gpu)
     assert bits_equal(got_x, want_x)
     assert bits_equal(got_s, want_s)
 

@@ -5,8 +5,10 @@ SeparableGT), CPU tier: nothing is launched.
 * Every argument rule of the entry point, called through the library with
   addresses that are never dereferenced (each refusal returns before a launch
   and names the entry), and DOL_OK for the empty shapes.
-* The rules of ops.gt_ring and SeparableGT, with ops._native.call replaced by
-  test_ops_args_gpu.Recorder.
+* The rules of ops.gt_ring that are the ring's own (halos, three rows) and of
+  SeparableGT, with ops._native.call replaced by test_ops_args_gpu.Recorder;
+  the rules it shares with ops.gt_csr_pm and ops.gt_csr (objective, aliased
+  state, weight vectors, CPU tensors) are in tests/test_gt_host.py.
 * The launch geometry and indexing of csrc/gt_ring.hip restated in the manner
   of tests/test_kernel_extents.py: gt_ring_dma_kernel<4, OBJ, SELF> (grid
   nct * cdiv(n, 4) in panels of 512 column tiles; R + 2 window rows of X and of S per block at
@@ -37,7 +39,7 @@ from dolhip.ops import DolNativeError
 from dolhip.synthetic import SeparableGT, ring_gt_weights
 from test_codegen_pins import _disasm, _kernels, _unbundle
 from test_kernel_extents import KT, Ext, cdiv
-from test_ops_args_gpu import Recorder, mat, vec
+from test_ops_args_gpu import vec
 
 CPU = torch.device("cpu")
 F32 = np.float32
@@ -115,48 +117,15 @@ def test_entry_point_checks_arguments_without_launch():
 # ---------------------------------------------------------------------------
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    monkeypatch.setattr(ops._native, "call", r)
-    return r
+    return gt_cases.recorder(monkeypatch)
 
 
-def _args(dev, n=4, P=10, ld=12):
-    return dict(X=mat(dev, n, P, ld), S=mat(dev, n, P, ld), XO=mat(dev, n, P, ld), SO=mat(dev, n, P, ld),
-                w_prev=vec(dev, n), w_next=vec(dev, n), target=mat(dev, n, P, ld))
+def _args(dev, n=4):
+    return gt_cases.host_args("gt_ring", dev, n)
 
 
 def _call(t, **kw):
-    return ops.gt_ring(t["X"], t["S"], t["XO"], t["SO"], t["w_prev"], t["w_next"], t["target"], **kw)
-
-
-def test_unknown_objective_is_refused(rec):
-    with pytest.raises(ValueError, match="gt_ring: objective must be one of"):
-        _call(_args(CPU), objective="hinge")
-    assert rec.calls == []
-
-
-@pytest.mark.parametrize("a,b", [("X", "S"), ("X", "XO"), ("X", "SO"), ("S", "XO"), ("S", "SO"), ("XO", "SO")])
-def test_two_state_matrices_the_same_tensor_are_refused(a, b, rec):
-    t = _args(CPU)
-    t[b] = t[a]
-    with pytest.raises(ValueError, match=f"gt_ring: {a} and {b} alias"):
-        _call(t)
-    assert rec.calls == []
-
-
-@pytest.mark.parametrize("name", ["w_prev", "w_next", "self_weight"])
-@pytest.mark.parametrize("bad", [lambda: vec(CPU, 3), lambda: vec(CPU, 4, torch.float64),
-                                 lambda: torch.zeros(4, device="meta"), lambda: vec(CPU, 8)[::2]],
-                         ids=["length", "dtype", "device", "stride"])
-def test_bad_weight_vectors_are_refused(name, bad, rec):
-    t, kw = _args(CPU), {}
-    if name == "self_weight":
-        kw[name] = bad()
-    else:
-        t[name] = bad()
-    with pytest.raises(ValueError, match=rf"{name}: expected contiguous float32 \[4\] on cpu"):
-        _call(t, **kw)
-    assert rec.calls == []
+    return gt_cases.host_call("gt_ring", t, **kw)
 
 
 def test_halos_come_as_four_or_not_at_all(rec):
@@ -175,12 +144,6 @@ def test_a_wrap_around_ring_needs_three_rows(rec):
     # with halos one row is a valid block: the next refusal is the CPU tensor's
     with pytest.raises(DolNativeError, match="cpu"):
         _call(_args(CPU, n=1), halos=(vec(CPU, 10),) * 4)
-    assert rec.calls == []
-
-
-def test_cpu_tensors_are_refused(rec):
-    with pytest.raises(DolNativeError, match="cpu"):
-        _call(_args(CPU), self_weight=vec(CPU, 4), objective="logistic", lr=0.5, P=10, n_rows=4)
     assert rec.calls == []
 
 

@@ -1,12 +1,15 @@
-"""HBM bytes of the fused ring gradient-tracking round from rocprofv3 counter
-runs, one run per counter with nothing traced beside it:
-  rocprofv3 --pmc FETCH_SIZE -d DIR/FETCH_SIZE -o run --output-format csv -- python tools/gt_ring_ab.py --legs a ...
-  rocprofv3 --pmc WRITE_SIZE -d DIR/WRITE_SIZE -o run --output-format csv -- python tools/gt_ring_ab.py --legs a ...
-  python tools/gt_ring_counters.py DIR --agents N [--params P] [--out profiles/gt_ring_counters.json]
-Medians per launch of gt_ring_dma_kernel, in KiB, per objective (the kernel's
-second template argument), against the algorithmic 3 N P 4 read and 2 N P 4
-written.  FETCH_SIZE counts half the bytes of a wide streaming read on gfx950,
-so `read_over_algorithmic` doubles it."""
+"""HBM bytes of the fused gradient-tracking round on an agent-major bank from
+rocprofv3 counter runs, one run per counter with nothing traced beside it (no
+tracing option in the same run; the program after `--`):
+  rocprofv3 --pmc FETCH_SIZE -d DIR/FETCH_SIZE -o run --output-format csv -- python tools/gt_ab.py --layout L --legs a ...
+  rocprofv3 --pmc WRITE_SIZE -d DIR/WRITE_SIZE -o run --output-format csv -- python tools/gt_ab.py --layout L --legs a ...
+  python tools/gt_counters.py DIR --layout L --agents N [--params P] [--out profiles/gt_L_counters.json]
+Medians per launch, in KiB, per objective, of the layout's f4 kernel: L = ring
+gt_ring_dma_kernel (the objective is its second template argument), L = csr
+gt_csr_xcd_kernel (the pinned tiles: every f4 column at P = 2^20; its third),
+against the algorithmic 3 N P 4 read and 2 N P 4 written.  FETCH_SIZE counts
+half the bytes of a wide streaming read on gfx950, so `read_over_algorithmic`
+doubles it."""
 import argparse
 import csv
 import glob
@@ -15,19 +18,25 @@ import re
 import statistics
 
 
+# the measured kernel's demangled name up to its objective, the one group
+KERNELS = {"ring": r"gt_ring_dma_kernel<\d+, (\d+)", "csr": r"gt_csr_xcd_kernel<\d+, \d+, (\d+)"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dir")
+    ap.add_argument("--layout", required=True, choices=sorted(KERNELS))
     ap.add_argument("--agents", type=int, required=True)
     ap.add_argument("--params", type=int, default=1 << 20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    kernel = KERNELS[a.layout]
     vals = {}
     for f in glob.glob(f"{a.dir}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            m = re.search(r"gt_ring_dma_kernel<(\d+), (\d+)", r["Kernel_Name"])
+            m = re.search(kernel, r["Kernel_Name"])
             if m:
-                obj = ("least_squares", "logistic")[int(m.group(2))]
+                obj = ("least_squares", "logistic")[int(m.group(1))]
                 vals.setdefault(obj, {}).setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     read_kib, write_kib = 3 * a.agents * a.params * 4 // 1024, 2 * a.agents * a.params * 4 // 1024
     res = {"agents": a.agents, "params": a.params, "algorithmic_read_KiB": read_kib, "algorithmic_write_KiB": write_kib,
