@@ -257,6 +257,42 @@ __device__ __forceinline__ void gt_finish(f4 ax, f4 as, f4 x, f4 s, f4 t, D d, b
   }
 }
 
+// The push-sum gradient-tracking round (ADD-OPT / Push-DIGing) on one coordinate
+// after its two mixes au = (C_off u), as = (C_off s), written once
+// (gt_push_csr_*_kernel): gt_finish with the gradient taken at the de-biased
+// estimate z = u / v instead of at u.  v: the agent's push-sum weight before
+// the round, av: after it (C v, self term included; the caller computes it
+// once per agent).  All fp32, each operation rounded once, the divisions
+// correctly rounded (a zero v divides like IEEE):
+//   self:  au = fl(au + fl(d u));  as = fl(as + fl(d s))
+//   u' = fma(-lr, s, au)
+//   z = u / v;  z' = u' / av
+//   s' = fl(fl(as + g(z', t)) - g(z, t))                     g = separable_grad<OBJ>
+template <int OBJ>
+__device__ __forceinline__ void gt_push_finish(float au, float as, float u, float s, float t, float d, bool self,
+                                               float neg_lr, float v, float av, float& uo, float& so) {
+  if (self) {
+    au = au + d * u;
+    as = as + d * s;
+  }
+  uo = __builtin_fmaf(neg_lr, s, au);
+  const float z = __fdiv_rn(u, v);
+  const float zo = __fdiv_rn(uo, av);
+  so = (as + separable_grad<OBJ>(zo, t)) - separable_grad<OBJ>(z, t);
+}
+// the same on four coordinates of one agent
+template <int OBJ>
+__device__ __forceinline__ void gt_push_finish(f4 au, f4 as, f4 u, f4 s, f4 t, float d, bool self, float neg_lr,
+                                               float v, float av, f4& uo, f4& so) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float ue, se;
+    gt_push_finish<OBJ>(au[j], as[j], u[j], s[j], t[j], d, self, neg_lr, v, av, ue, se);
+    uo[j] = ue;
+    so[j] = se;
+  }
+}
+
 // The local steps on one coordinate: the one place this arithmetic is written
 // (DgdEpi on the agent-major bank, csr_pm_kernel on the parameter-major one).
 // e: the epilogue's arguments, read where they are used (e.steps, e.mom, e.neg_lr).

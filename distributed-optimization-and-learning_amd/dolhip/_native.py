@@ -95,6 +95,8 @@ SIGNATURES = {
                         _ptr, _ptr, _i64, _i32, _f32, _ptr],
     "dol_gt_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
                        _i32, _f32, _ptr],
+    "dol_gt_push_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                            _i64, _i32, _f32, _ptr, _ptr, _ptr],
     "dol_separable_grad_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i32, _ptr],
     "dol_transpose_f32": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr],
     "dol_csr_slab_nk": [_i32],

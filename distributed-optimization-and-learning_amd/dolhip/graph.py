@@ -230,6 +230,21 @@ class CSR:
         d[rows, self.col] = self.val
         return d
 
+    def transpose(self) -> "CSR":
+        """The CSR of the transposed matrix (a host operation): row j lists
+        the entries of column j in ascending row order, values unchanged.  A
+        row-stochastic W becomes column-stochastic, which is what the push-sum
+        round needs (ops.gt_push_csr).  Transposing twice gives back a CSR
+        whose columns ascend within each row."""
+        self.validate()
+        rows = np.repeat(np.arange(self.n_rows, dtype=np.int64), np.diff(np.asarray(self.rowptr, np.int64)))
+        cols = np.asarray(self.col, np.int64)
+        order = np.lexsort((rows, cols))  # by column, then by row; stable
+        rowptr = np.zeros(self.n_cols + 1, np.int64)
+        np.cumsum(np.bincount(cols, minlength=self.n_cols), out=rowptr[1:])
+        return CSR(self.n_cols, self.n_rows, rowptr.astype(np.int32), rows[order].astype(np.int32),
+                   np.asarray(self.val, np.float32)[order]).validate()
+
 
 def csr_from_dense(W: Graph) -> CSR:
     """Neighbors (DIST/simulators.py:91-97) for all rows: j ascending, W[i][j] > 0."""
@@ -338,6 +353,34 @@ def metropolis_weights(csr: CSR):
         total[has] = total[has] + val[rowptr[:-1][has] + k]
     d = (np.float32(1.0) - total).astype(np.float32)
     return CSR(n, n, rowptr.astype(np.int32), c.astype(np.int32), val.astype(np.float32)), d
+
+
+def push_sum_weights(pattern: CSR):
+    """(C_off, d): the out-degree weights of push-sum on a directed graph, as a
+    zero-diagonal CSR and the self-weight vector d (float32 [n]), so that C =
+    C_off + diag(d) is column-stochastic -- what ops.gt_push_csr needs, and all
+    it needs: each agent builds its column from its own out-degree, and no
+    symmetry is asked of the graph (metropolis_weights refuses a directed one).
+    Row i of `pattern` lists i's in-neighbours: an entry (i, j) is the edge
+    j -> i.  Only the pattern is used; values, diagonal entries and duplicates
+    are ignored.  With outdeg_j the number of agents j sends to,
+      C_ij = fl(1 / (outdeg_j + 1))  for every edge j -> i, columns ascending
+      d_j  = fl(1 / (outdeg_j + 1))
+    so column j holds outdeg_j + 1 equal weights.  Not in the reference: its
+    "stochastic" W (DIST/simulators.py:40-86) is row-stochastic with random
+    weights; CSR.transpose() of it is the other column-stochastic choice."""
+    n = pattern.n_rows
+    if pattern.n_cols != n:
+        raise ValueError(f"push_sum_weights: the pattern must be square (got {n} x {pattern.n_cols})")
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(np.asarray(pattern.rowptr, np.int64)))
+    cols = np.asarray(pattern.col, np.int64)
+    off = rows != cols
+    edges = np.unique(rows[off] * n + cols[off])  # sorted by row, then column
+    r, c = edges // n, edges % n
+    share = np.float32(1.0) / (np.bincount(c, minlength=n) + 1).astype(np.float32)
+    rowptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(r, minlength=n), out=rowptr[1:])
+    return CSR(n, n, rowptr.astype(np.int32), c.astype(np.int32), share[c].astype(np.float32)), share
 
 
 def erdos_renyi_stochastic(n: int, p: float, generator: torch.Generator, device=None) -> torch.Tensor:
@@ -563,6 +606,23 @@ class MixingPlan:
         if self.kind == "dense":
             raise NotImplementedError("gradient-tracking rounds are fused into the sparse mixes; use a ring/CSR plan")
         return ops.gt_csr(X, S, XO, SO, self.rowptr, self.col, self.val, target, **kw)
+
+    def apply_gt_push(self, U: torch.Tensor, S: torch.Tensor, UO: torch.Tensor, SO: torch.Tensor,
+                      target: torch.Tensor, v: torch.Tensor, v_out: torch.Tensor,
+                      self_weight: Optional[torch.Tensor] = None, objective: str = "least_squares", lr: float = 0.01,
+                      P: Optional[int] = None):
+        """One push-sum gradient-tracking round (ops.gt_push_csr) with C = this
+        plan's matrix + diag(self_weight), column-stochastic; CSR plans only
+        (the ring kernel has no push-sum form: build the plan with
+        allow_ring=False).  Returns (UO, SO, v_out)."""
+        from . import ops
+        self._check_x(U)
+        if self.kind == "ring":
+            raise NotImplementedError("the push-sum round runs on a CSR plan; build this one with allow_ring=False")
+        if self.kind == "dense":
+            raise NotImplementedError("gradient-tracking rounds are fused into the sparse mixes; use a CSR plan")
+        return ops.gt_push_csr(U, S, UO, SO, self.rowptr, self.col, self.val, target, v, v_out,
+                               self_weight=self_weight, objective=objective, lr=lr, P=P)
 
 
 def plans_for(graphs: Sequence[Graph], device, allow_ring: bool = True) -> List[MixingPlan]:

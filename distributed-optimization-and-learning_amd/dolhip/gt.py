@@ -23,6 +23,11 @@ them for the three ops without a launch.  gt_ring's own rules are in its
 docstring and in tests/test_gt_ring_host.py, gt_csr's in its docstring and in
 tests/test_gt_csr_gpu.py (the ones a CPU tensor does not reach, with the
 library call recorded).
+
+gt_push_csr (dol_gt_push_csr_f32, ops.gt_push_csr) is the push-sum form of
+gt_csr's round for weights that are column-stochastic only (ADD-OPT /
+Push-DIGing): one more scalar per agent and the gradients taken at U / v; its
+arithmetic and rules are in its docstring, pinned by tests/test_gt_push_host.py.
 """
 from __future__ import annotations
 
@@ -164,6 +169,51 @@ def gt_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor,
                  P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
                  _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
     return XO, SO
+
+
+def gt_push_csr(U: torch.Tensor, S: torch.Tensor, UO: torch.Tensor, SO: torch.Tensor, rowptr: torch.Tensor,
+                col: torch.Tensor, val: torch.Tensor, target: torch.Tensor, v: torch.Tensor, v_out: torch.Tensor,
+                self_weight: Optional[torch.Tensor] = None, objective: str = "least_squares", lr: float = 0.01,
+                P: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One push-sum gradient-tracking round (ADD-OPT / Push-DIGing,
+    dol_gt_push_csr_f32) on the agent-major bank, for weights that are
+    column-stochastic only -- a directed graph, or the reference's
+    row-stochastic W transposed -- where gt_csr settles at a biased point.  U
+    the push-sum numerators, S the trackers, target the targets, [>= n, >= P]
+    like gt_csr's X; v the push-sum weights, n floats; UO / SO / v_out receive
+    u' / s' / v'.  C = C_off + diag(self_weight) is column-stochastic, C_off
+    the square CSR whose row i lists i's in-neighbours
+    (graph.push_sum_weights).  Per coordinate, all fp32, one rounding each
+      au = mix of u, as = mix of s                     (mix_csr's sums)
+      av = the same mix of the n-vector v
+      au = fl(au + fl(d_i u_i)), as = fl(as + fl(d_i s_i)), av = fl(av + fl(d_i v_i))     with self_weight
+      u' = fma(-lr, s_i, au)
+      z = u_i / v_i;  z' = u' / av                     (correctly rounded divisions)
+      s' = fl(fl(as + g(z', t_i)) - g(z, t_i));  v'_i = av
+    with g the gradient separable_grad computes.  The estimate z = U / v is not
+    stored.  Start from v = 1, U = x(0), S = g(x(0), t).  With v = 1 and av = 1
+    in every row the bits of gt_csr.  The rules of this op are gt_csr's (a
+    known objective; the four state matrices distinct; a self-weight vector of
+    n floats; a square C) and: v and v_out are n float32 values on the device,
+    and distinct.  Values are not checked: a zero v_i divides like IEEE.
+    Returns (UO, SO, v_out)."""
+    obj = _check_objective("gt_push_csr", objective)
+    n = rowptr.shape[0] - 1
+    state = (("U", U), ("S", S), ("UO", UO), ("SO", SO))
+    _distinct_state("gt_push_csr", state)
+    for nm, w in (("v", v), ("v_out", v_out)) + ((("self_weight", self_weight),) if self_weight is not None else ()):
+        _ops._check_array(nm, w, torch.float32, n, U.device)
+    if v is v_out or v.data_ptr() == v_out.data_ptr():
+        raise ValueError("gt_push_csr: v and v_out alias: every v' reads its neighbours' v")
+    P = U.shape[1] if P is None else P
+    ldu, ld_s, lduo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
+    _ops._check_csr(rowptr, col, val, U.device, same_length=False)
+    _check_square(rowptr, col, n)
+    _native.call("dol_gt_push_csr_f32", U.data_ptr(), ldu, S.data_ptr(), ld_s, UO.data_ptr(), lduo, SO.data_ptr(), ldso,
+                 n, P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
+                 _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), v.data_ptr(), v_out.data_ptr(),
+                 _ops._stream(U))
+    return UO, SO, v_out
 
 
 def separable_grad(X: torch.Tensor, T: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -850,6 +850,80 @@ class SeparableGT(SeparableGTCSR):
                              f"sparse W of up to {ops.GT_MAX_AGENTS} agents")
 
 
+class SeparableGTPush:
+    """Config 3 with push-sum gradient tracking (ADD-OPT / Push-DIGing) on the
+    agent-major bank: SeparableGTCSR's sibling for weights that are
+    column-stochastic only, one call and one pass over U, S and the targets per
+    round through plan.apply_gt_push (dol_gt_push_csr_f32).  Not a reference
+    algorithm.
+
+    plan is a CSR plan (MixingPlan(..., allow_ring=False) where the pattern is
+    a ring); C = its matrix + diag(self_weight) must be column-stochastic with
+    a positive diagonal on a strongly connected graph: graph.push_sum_weights
+    gives that from any directed pattern, and CSR.transpose() of the
+    reference's row-stochastic W, halved, with self weights 1/2, from its own
+    graphs.  On such weights SeparableGTCSR settles at a biased point.
+
+    The bank holds u / u_out (the push-sum numerators in and out), s / s_out
+    (trackers) and target, with SeparableDGD's seeded init (u starts as x(0));
+    v / v_out are the push-sum weights, n floats each, starting at 1; s starts
+    as ops.separable_grad(x(0), target).  The estimate every agent holds is
+    params() = u / v."""
+
+    def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
+                 self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
+        from . import ops
+        if plan.kind == "dense":
+            raise ValueError("the gradient-tracking round mixes a sparse (CSR) W")
+        if plan.kind == "ring":
+            raise ValueError("SeparableGTPush runs on a CSR plan (got kind 'ring'); build it with allow_ring=False")
+        self.plan, self.objective, self.lr = plan, objective, float(lr)
+        self.N = plan.n_rows
+        dev = plan.device
+        self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
+        self.bank = bank if bank is not None else AgentBank(self.N, P, dev)
+        self.P = self.bank.P
+        _seeded_draw(self.bank.buffer("u"), self.bank.buffer("target"), objective, seed, dev)
+        for name in ("u_out", "s", "s_out"):
+            self.bank.buffer(name, zero=True)
+        self.v = torch.ones(self.N, dtype=torch.float32, device=dev)
+        self.v_out = torch.ones(self.N, dtype=torch.float32, device=dev)
+        ops.separable_grad(self.bank.rows("u"), self.bank.rows("target"), self.bank.rows("s"), objective)
+        self.rounds = 0
+
+    def round(self) -> None:
+        """One push-sum gradient-tracking round (one call); swaps u / u_out, s / s_out and v / v_out."""
+        b = self.bank
+        self.plan.apply_gt_push(b.buffer("u"), b.buffer("s"), b.buffer("u_out"), b.buffer("s_out"), b.buffer("target"),
+                                self.v, self.v_out, self_weight=self.self_weight, objective=self.objective, lr=self.lr,
+                                P=self.P)
+        b.swap("u", "u_out")
+        b.swap("s", "s_out")
+        self.v, self.v_out = self.v_out, self.v
+        self.rounds += 1
+
+    def params(self) -> torch.Tensor:
+        """The agents' estimates z = u / v (a read-out: torch's division)."""
+        return self.bank.rows("u") / self.v[:, None]
+
+    def tracker(self) -> torch.Tensor:
+        return self.bank.rows("s")
+
+    def weights(self) -> torch.Tensor:
+        return self.v
+
+    def targets(self) -> torch.Tensor:
+        return self.bank.rows("target")
+
+    def consensus_error(self) -> float:
+        x = self.params()
+        return float((x - x.mean(0, keepdim=True)).norm() / max(1, x.shape[0]) ** 0.5)
+
+    def distance_to_optimum(self) -> float:
+        """_distance_to_mean_target of the estimates (agents along axis 0)."""
+        return _distance_to_mean_target(self.params(), self.targets(), 0, self.objective)
+
+
 class TimeVaryingMLPGossip:
     """BASELINE config 5 as a first-class round: N agents, each an
     nn.Sequential(Linear(d, h), ReLU(), Linear(h, c)) row of the bank, a new

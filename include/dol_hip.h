@@ -445,6 +445,39 @@ int dol_gt_csr_f32(const float* X, int64_t ldx, const float* S, int64_t lds, flo
                    float lr, hipStream_t s);
 
 /*
+ * One push-sum gradient-tracking round of BASELINE config 3 on the agent-major
+ * bank in one pass, for weights that are column-stochastic only (directed
+ * graphs, the reference's row-stochastic W transposed): ADD-OPT (Xi, Xin, Khan,
+ * IEEE TAC 63(5), 2018) / Push-DIGing (Nedic, Olshevsky, Shi, SIAM J. Optim.
+ * 27(4), 2017) in combine-then-adapt form.  Not in the reference: its
+ * decentralised round is consensus + local step (DIST/simulators.py:147-162),
+ * and on the row-stochastic W of its default "stochastic" mode
+ * (DIST/simulators.py:40-86) dol_gt_csr_f32's recursion settles at a biased
+ * point.  U (push-sum numerators), S (trackers), UO, SO and target are row
+ * matrices of n rows in dol_gt_csr_f32's layout; v, v_out: one push-sum weight
+ * per agent, n floats each; C = C_off + diag(self_w), C_off the square CSR
+ * whose row i lists i's in-neighbours.  For every row i and column c, all fp32,
+ * each operation rounded once:
+ *   au = sum_e val[e] * u[col[e]]      (+0 start, ascending e, product and sum rounded separately)
+ *   as = the same over s;   av = the same over the vector v
+ *   self_w != NULL:  au = fl(au + fl(self_w[i]*u_i));  as, av likewise
+ *   u' = fma(-lr, s_i, au)
+ *   z = u_i / v_i;   z' = u' / av                        (correctly rounded divisions)
+ *   s' = fl(fl(as + g(z', t_i)) - g(z, t_i))             g as dol_separable_grad_f32
+ *   v_out[i] = av
+ * The estimate z = U / v is not stored.  Start: v = 1, U = x(0), S = g(x(0), t).
+ * With v = 1 and av = 1 in every row the bits of dol_gt_csr_f32.  Argument rules
+ * as dol_gt_csr_f32, and: v, v_out not null and distinct.  Values are not
+ * validated: a zero v_i divides like IEEE.  A small kernel writes v_out first;
+ * the round then streams U, S, target in and UO, SO out once.  Stream-ordered;
+ * allocates nothing; does not synchronise.
+ */
+int dol_gt_push_csr_f32(const float* U, int64_t ldu, const float* S, int64_t lds, float* UO, int64_t lduo, float* SO,
+                        int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                        const float* val, const float* self_w /* nullable */, const float* target, int64_t ldt,
+                        int32_t objective, float lr, const float* v, float* v_out, hipStream_t s);
+
+/*
  * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the
  * separable losses of dol_dgd_ring_f32 (objective 0: fl(x - t), 1:
  * -t / (1 + exp(t x)), the same device code).  Elementwise, so it serves the
