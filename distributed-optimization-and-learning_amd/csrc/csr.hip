@@ -1,5 +1,5 @@
 // csr.hip — the generic sparse (CSR) mix on the agent-major bank and its
-// fused DGD round: 4 KiB column tiles, or XCD-pinned 512 B tiles from 512 rows.
+// fused DGD and EXTRA rounds: 4 KiB column tiles, or XCD-pinned 512 B tiles from 512 rows.
 //
 // Dropped launch variant (8192 x 2^20; the default's bits; code last present at 1a824fc):
 //   DOL_CSR_PASSES=1|4: csr_xcd_kernel with 8 / 32 rows per block instead of 16: 512-B tiles 17.94 ms
@@ -214,6 +214,18 @@ int dol_dgd_csr_f32(const float* X, int64_t ldx, int32_t x_rows, float* Y, int64
   const DgdArgs d{target, ldt, mom, ldm, objective, local_steps, lr, momentum, first_step};
   return with_dgd_epi(nm, d, n_rows <= 0 || P <= 0, P, [&](auto epi, bool evec) {
     return mix_csr_impl(nm, X, ldx, x_rows, Y, ldy, n_rows, P, rowptr, col, val, epi, evec, s);
+  });
+}
+
+// the EXTRA round (ExtraEpi, dol_launch.h): W is square, so the centre of output row i is row i of X
+int dol_extra_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n, int64_t P, const int32_t* rowptr,
+                      const int32_t* col, const float* val, const float* self_w, const float* target, int64_t ldt,
+                      float* corr, int64_t ldc, int32_t objective, float lr, hipStream_t s) {
+  DOL_DIMS_OK("dol_extra_csr_f32", ldx, ldy, P, ldt, ldc);
+  const char* nm = "dol_extra_csr_f32";
+  const ExtraArgs e{target, ldt, corr, ldc, self_w, objective, lr};
+  return with_extra_epi<false>(nm, e, X, ldx, Y, n <= 0 || P <= 0, P, [&](auto epi, bool evec) {
+    return mix_csr_impl(nm, X, ldx, n, Y, ldy, n, P, rowptr, col, val, epi, evec, s);
   });
 }
 

@@ -293,6 +293,37 @@ __device__ __forceinline__ void gt_push_finish(f4 au, f4 as, f4 u, f4 s, f4 t, f
   }
 }
 
+// The EXTRA round (Shi, Ling, Wu, Yin, SIAM J. Optim. 25(2), 2015) on one
+// coordinate after its one mix ax = (W_off x), written once (ExtraEpi below, so
+// every agent-major mix kernel that takes an epilogue).  With W~ = (I + W) / 2
+// the method's two-step recursion is x' = W x - lr g(x) - c, c' = c + (x - W x) / 2,
+// c(0) = 0: the correction c is the agent's own row, so only x is mixed.  All
+// fp32, each operation rounded once, d the agent's self weight:
+//   self:  ax = fl(ax + fl(d x))
+//   r  = fl(x - ax)
+//   x' = fl(fma(-lr, g(x, t), ax) - c)                       g = separable_grad<OBJ>
+//   c' = fma(0.5, r, c)
+template <int OBJ>
+__device__ __forceinline__ void extra_finish(float ax, float x, float c, float t, float d, bool self, float neg_lr,
+                                             float& xo, float& co) {
+  if (self) ax = ax + d * x;
+  const float r = x - ax;
+  xo = __builtin_fmaf(neg_lr, separable_grad<OBJ>(x, t), ax) - c;
+  co = __builtin_fmaf(0.5f, r, c);
+}
+// the same on four coordinates of one agent
+template <int OBJ>
+__device__ __forceinline__ void extra_finish(f4 ax, f4 x, f4 c, f4 t, float d, bool self, float neg_lr, f4& xo,
+                                             f4& co) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float xe, ce;
+    extra_finish<OBJ>(ax[j], x[j], c[j], t[j], d, self, neg_lr, xe, ce);
+    xo[j] = xe;
+    co[j] = ce;
+  }
+}
+
 // The local steps on one coordinate: the one place this arithmetic is written
 // (DgdEpi on the agent-major bank, csr_pm_kernel on the parameter-major one).
 // e: the epilogue's arguments, read where they are used (e.steps, e.mom, e.neg_lr).
@@ -311,16 +342,46 @@ __device__ __forceinline__ float dgd_local_steps(float x, float t, float& b, con
   return x;
 }
 
+// An epilogue whose kCentre is true takes the mixed row's own value from a
+// kernel that holds it in registers (the ring kernels' stencil window) through
+// apply_centre(y, centre, state, r, cf); the others, and every kernel without
+// such a window, use apply().  The kernels branch on it with `if constexpr`,
+// their apply() call left as it was.
 struct Empty {};
 struct NoEpi {
+  static constexpr bool kCentre = false;
   template <typename V> __device__ __forceinline__ Empty load(int, int64_t) const { return {}; }
   template <typename V> __device__ __forceinline__ V apply(V y, Empty, int, int64_t) const { return y; }
 };
+
+// One read-once element of an epilogue's own row (targets, momentum,
+// corrections) under the policy DgdEpi's comment below measures: nt 3 = buffer
+// load with aux 3 (sc0 nt), 1 = the compiler's nontemporal global load, 0 =
+// plain.  Scalar columns always load plainly.
+template <typename V>
+__device__ __forceinline__ V epi_ld(int nt, const float* row, int64_t cf) {
+  const V* p = reinterpret_cast<const V*>(row + cf);
+  if constexpr (sizeof(V) == 16) {
+    if (nt == 3) {
+      const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, 0x7ffffff0, 0x00020000);
+      return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, uint32_t(cf) * 4u, 0, 3));
+    }
+    if (nt == 1) return __builtin_nontemporal_load(p);
+  }
+  return *p;
+}
+// DOL_DGD_EPI_NT (default 3) for rows of P floats: buffer offsets are 32-bit
+// (rows of < 2^29 floats); longer rows take plain loads
+inline int epi_nt_policy(int64_t P) {
+  static const int nt_env = env_int("DOL_DGD_EPI_NT", 3);
+  return (nt_env == 3 && P > (int64_t(1) << 29) - 16) ? 0 : nt_env;
+}
 
 template <typename V> struct DgdState { V t, b; };
 
 template <int OBJ, int MODE>
 struct DgdEpi {
+  static constexpr bool kCentre = false;
   const float* __restrict__ T; int64_t ldt;
   float* __restrict__ M; int64_t ldm;
   float neg_lr, mom;
@@ -337,15 +398,7 @@ struct DgdEpi {
   int nt;
 
   template <typename V> __device__ __forceinline__ V ld(const float* row, int64_t cf) const {
-    const V* p = reinterpret_cast<const V*>(row + cf);
-    if constexpr (sizeof(V) == 16) {
-      if (nt == 3) {
-        const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, 0x7ffffff0, 0x00020000);
-        return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rs, uint32_t(cf) * 4u, 0, 3));
-      }
-      if (nt == 1) return __builtin_nontemporal_load(p);
-    }
-    return *p;
+    return epi_ld<V>(nt, row, cf);
   }
   template <typename V> __device__ __forceinline__ DgdState<V> load(int r, int64_t cf) const {
     DgdState<V> st;
@@ -397,12 +450,93 @@ int with_dgd_epi(const char* nm, const DgdArgs& d, bool empty, int64_t P, F&& f)
     const int rc = check_dgd(nm, d, P, &evec, &mode);
     if (rc) return rc;
   }
-  static const int nt_env = env_int("DOL_DGD_EPI_NT", 3);
-  // buffer offsets are 32-bit (rows of < 2^29 floats); longer rows: plain loads
-  const int nt = (nt_env == 3 && P > (int64_t(1) << 29) - 16) ? 0 : nt_env;
+  const int nt = epi_nt_policy(P);
   return dispatch([&](auto obj, auto md) {
     return f(DgdEpi<decltype(obj)::value, decltype(md)::value>{d.T, d.ldt, d.M, d.ldm, -d.lr, d.momentum, d.steps, nt}, evec);
   }, Ints<0, 1>{d.objective}, Ints<0, 1, 2>{mode});
+}
+
+// ExtraEpi: the EXTRA round (extra_finish above) as a mixing epilogue.  After
+// the mix of row r it needs that row's own x, its correction c (read and
+// written in place, like DgdEpi's M) and its target t.  t and c are read once:
+// DgdEpi's nontemporal policy (epi_ld).  The centre x: CENTRE = false loads it
+// in load() with the default policy (it is another row's neighbour) -- the CSR
+// kernels and the ring's edge kernel, which do not hold it; CENTRE = true takes
+// it from the kernel's stencil window through apply_centre (ring_mix_dma_kernel,
+// ring_mix_kernel), which saves the second read of the row and a third of the
+// epilogue's registers.
+template <typename V> struct ExtraState { V t, c, x; };
+
+template <int OBJ, bool SELF, bool CENTRE>
+struct ExtraEpi {
+  static constexpr bool kCentre = CENTRE;
+  const float* __restrict__ T; int64_t ldt;
+  float* __restrict__ C; int64_t ldc;
+  const float* __restrict__ X; int64_t ldx;
+  const float* __restrict__ self_w;
+  float neg_lr;
+  int nt;
+
+  template <typename V> __device__ __forceinline__ ExtraState<V> load(int r, int64_t cf) const {
+    ExtraState<V> st;
+    st.t = epi_ld<V>(nt, T + int64_t(r) * ldt, cf);
+    st.c = epi_ld<V>(nt, C + int64_t(r) * ldc, cf);
+    if constexpr (CENTRE) st.x = vzero(V{});
+    else st.x = *reinterpret_cast<const V*>(X + int64_t(r) * ldx + cf);
+    return st;
+  }
+  template <typename V>
+  __device__ __forceinline__ V apply_centre(V y, V centre, ExtraState<V> st, int r, int64_t cf) const {
+    st.x = centre;
+    return apply(y, st, r, cf);
+  }
+  template <typename V> __device__ __forceinline__ V apply(V y, ExtraState<V> st, int r, int64_t cf) const {
+    float d = 0.0f;
+    if constexpr (SELF) d = self_w[r];
+    V xo, co;
+    extra_finish<OBJ>(y, st.x, st.c, st.t, d, SELF, neg_lr, xo, co);
+    __builtin_nontemporal_store(co, reinterpret_cast<V*>(C + int64_t(r) * ldc + cf));
+    return xo;
+  }
+};
+
+// validation + dispatch of the EXTRA round (mix + extra_finish)
+struct ExtraArgs {
+  const float* T; int64_t ldt; float* C; int64_t ldc; const float* self_w;
+  int32_t objective; float lr;
+};
+
+// X, Y: the mix's own pair (the mix's preamble checks them; here only against corr)
+inline int check_extra(const char* nm, const ExtraArgs& e, const float* X, const float* Y, int64_t P, bool* evec) {
+  if (!e.T) return fail(DOL_EINVAL, "%s: null target", nm);
+  if (!e.C) return fail(DOL_EINVAL, "%s: null corr", nm);
+  if (e.objective != 0 && e.objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 (least squares) or 1 (logistic)", nm);
+  if (e.ldt < P) return fail(DOL_EINVAL, "%s: ldt < P", nm);
+  if (e.ldc < P) return fail(DOL_EINVAL, "%s: ldc < P", nm);
+  if (e.C == X || e.C == Y || e.C == e.T)
+    return fail(DOL_EINVAL, "%s: corr aliases X, Y or target (the correction is updated in place)", nm);
+  *evec = row_vec_ok(e.T, e.ldt) && row_vec_ok(e.C, e.ldc);
+  return DOL_OK;
+}
+
+// Checks e (unless the problem is empty: the mix's own preamble then answers)
+// and calls f(epi, epi_vec_ok) with the epilogue of e's objective and of
+// whether self weights are given; X / ldx: the rows the mix reads, whose row r
+// is the centre of output row r.  CENTRE: whether the kernels f launches hand
+// that row to the epilogue themselves (ExtraEpi).
+template <bool CENTRE, class F>
+int with_extra_epi(const char* nm, const ExtraArgs& e, const float* X, int64_t ldx, const float* Y, bool empty,
+                   int64_t P, F&& f) {
+  bool evec = false;
+  if (!empty) {
+    const int rc = check_extra(nm, e, X, Y, P, &evec);
+    if (rc) return rc;
+  }
+  const int nt = epi_nt_policy(P);
+  return dispatch([&](auto obj, auto self) {
+    return f(ExtraEpi<decltype(obj)::value, decltype(self)::value, CENTRE>{e.T, e.ldt, e.C, e.ldc, X, ldx, e.self_w, -e.lr, nt},
+             evec);
+  }, Ints<0, 1>{e.objective}, Bool{e.self_w != nullptr});
 }
 
 }  // namespace

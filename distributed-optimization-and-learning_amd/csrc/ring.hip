@@ -1,5 +1,5 @@
-// ring.hip — the ring (circle-graph) mixes: one round, its fused DGD round,
-// the two edge rows of a sharded ring, and eps rounds in one pass.
+// ring.hip — the ring (circle-graph) mixes: one round, its fused DGD and EXTRA
+// rounds, the two edge rows of a sharded ring, and eps rounds in one pass.
 //
 // Layout: agent k's parameter vector is row k of a row-major fp32 matrix
 // with leading dimension ld (elements).  Columns are streamed 16 B per lane
@@ -85,7 +85,8 @@ __global__ __launch_bounds__(kThreads) void ring_mix_kernel(
       if (r < r1) {
         V out = axpy0(wprev[r], q[k], wnext[r], q[k + 2]);
         const int64_t cf = c_off + c * Vec<V>::W;
-        out = epi.apply(out, epi.template load<V>(r, cf), r, cf);
+        if constexpr (Epi::kCentre) out = epi.apply_centre(out, q[k + 1], epi.template load<V>(r, cf), r, cf);
+        else out = epi.apply(out, epi.template load<V>(r, cf), r, cf);
         __builtin_nontemporal_store(out, reinterpret_cast<V*>(Y + int64_t(r) * ldy + c_off) + c);
       }
     }
@@ -173,9 +174,15 @@ __global__ __launch_bounds__(kThreads) void ring_mix_dma_kernel(
 #pragma unroll
   for (int k = 0; k < R; ++k) {
     const int r = r0 + k;
-    if (r < r1)
-      __builtin_nontemporal_store(COPY ? v[k + 1] : epi.apply(axpy0(wprev[r], v[k], wnext[r], v[k + 2]), es[k], r, 4 * c),
-                                  reinterpret_cast<f4*>(Y + int64_t(r) * ldy) + c);
+    if constexpr (Epi::kCentre) {  // the epilogue takes the row's own x from the tile
+      if (r < r1)
+        __builtin_nontemporal_store(epi.apply_centre(axpy0(wprev[r], v[k], wnext[r], v[k + 2]), v[k + 1], es[k], r, 4 * c),
+                                    reinterpret_cast<f4*>(Y + int64_t(r) * ldy) + c);
+    } else {
+      if (r < r1)
+        __builtin_nontemporal_store(COPY ? v[k + 1] : epi.apply(axpy0(wprev[r], v[k], wnext[r], v[k + 2]), es[k], r, 4 * c),
+                                    reinterpret_cast<f4*>(Y + int64_t(r) * ldy) + c);
+    }
   }
 }
 
@@ -594,6 +601,31 @@ int dol_dgd_ring_edges_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, i
   const char* nm = "dol_dgd_ring_edges_f32";
   const DgdArgs d{target, ldt, mom, ldm, objective, local_steps, lr, momentum, first_step};
   return with_dgd_epi(nm, d, n_rows <= 0 || P <= 0, P, [&](auto epi, bool evec) {
+    return ring_edges_impl(nm, X, ldx, Y, ldy, n_rows, P, halo_prev, halo_next, w_prev, w_next, epi, evec, s);
+  });
+}
+
+// the EXTRA round (ExtraEpi, dol_launch.h) on the ring, wrap-around or with halos, and its two boundary rows
+int dol_extra_ring_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n_rows, int64_t P,
+                       const float* halo_prev, const float* halo_next, const float* w_prev, const float* w_next,
+                       const float* w_self, const float* target, int64_t ldt, float* corr, int64_t ldc,
+                       int32_t objective, float lr, hipStream_t s) {
+  DOL_DIMS_OK("dol_extra_ring_f32", ldx, ldy, P, ldt, ldc);
+  const char* nm = "dol_extra_ring_f32";
+  const ExtraArgs e{target, ldt, corr, ldc, w_self, objective, lr};
+  return with_extra_epi<true>(nm, e, X, ldx, Y, n_rows <= 0 || P <= 0, P, [&](auto epi, bool evec) {
+    return mix_ring_impl(nm, X, ldx, Y, ldy, n_rows, P, halo_prev, halo_next, w_prev, w_next, epi, evec, s);
+  });
+}
+
+int dol_extra_ring_edges_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n_rows, int64_t P,
+                             const float* halo_prev, const float* halo_next, const float* w_prev,
+                             const float* w_next, const float* w_self, const float* target, int64_t ldt, float* corr,
+                             int64_t ldc, int32_t objective, float lr, hipStream_t s) {
+  DOL_DIMS_OK("dol_extra_ring_edges_f32", ldx, ldy, P, ldt, ldc);
+  const char* nm = "dol_extra_ring_edges_f32";
+  const ExtraArgs e{target, ldt, corr, ldc, w_self, objective, lr};
+  return with_extra_epi<false>(nm, e, X, ldx, Y, n_rows <= 0 || P <= 0, P, [&](auto epi, bool evec) {
     return ring_edges_impl(nm, X, ldx, Y, ldy, n_rows, P, halo_prev, halo_next, w_prev, w_next, epi, evec, s);
   });
 }

@@ -12,7 +12,8 @@ Layers:
             and SeparableScaffold (ops.scaffold_ls_round); gradient tracking:
             SeparableGT (agent-major ring, ops.gt_ring), SeparableGTCSR (agent-major
             bank, any sparse W, ops.gt_csr), SeparableGTPM, and SeparableGTPush
-            (push-sum, column-stochastic weights, ops.gt_push_csr)
+            (push-sum, column-stochastic weights, ops.gt_push_csr); EXTRA, which
+            mixes the parameters only: SeparableEXTRA (ops.extra_csr / ops.extra_ring)
 The reference-shaped APIs live beside this package:
   weighted_average/  (Simulator, DecFedAvg, FedLCon, Client, ...)
   primal_dual/       (Server, FedAvg_/FedProx_/FedAdmm_Server/_Client)
@@ -21,6 +22,6 @@ from ._native import DolNativeError, build, lib  # noqa: F401
 from . import ops, graph, bank  # noqa: F401
 from .bank import AgentBank  # noqa: F401
 from .graph import MixingPlan, communication_graph, csr_from_dense  # noqa: F401
-from .synthetic import SeparableGT, SeparableGTCSR, SeparableGTPush, SeparableScaffold  # noqa: F401
+from .synthetic import SeparableEXTRA, SeparableGT, SeparableGTCSR, SeparableGTPush, SeparableScaffold  # noqa: F401
 
 __version__ = "0.1.0"

@@ -607,6 +607,22 @@ class MixingPlan:
             raise NotImplementedError("gradient-tracking rounds are fused into the sparse mixes; use a ring/CSR plan")
         return ops.gt_csr(X, S, XO, SO, self.rowptr, self.col, self.val, target, **kw)
 
+    def apply_extra(self, X: torch.Tensor, Y: torch.Tensor, target: torch.Tensor, corr: torch.Tensor,
+                    self_weight: Optional[torch.Tensor] = None, objective: str = "least_squares", lr: float = 0.01,
+                    P: Optional[int] = None) -> torch.Tensor:
+        """One EXTRA round (ops.extra_ring / ops.extra_csr) with W = this
+        plan's W + diag(self_weight); ring or CSR.  corr is updated in place.
+        A CSR plan that carries a slab pack still runs ops.extra_csr: the
+        LDS-gather kernel has no epilogue.  Returns Y."""
+        from . import ops
+        self._check_x(X)
+        kw = dict(self_weight=self_weight, objective=objective, lr=lr, P=P)
+        if self.kind == "ring":
+            return ops.extra_ring(X, Y, self.w_prev, self.w_next, target, corr, n_rows=self.n_rows, **kw)
+        if self.kind == "dense":
+            raise NotImplementedError("EXTRA rounds are fused into the sparse mixes; use a ring/CSR plan")
+        return ops.extra_csr(X, Y, self.rowptr, self.col, self.val, target, corr, **kw)
+
     def apply_gt_push(self, U: torch.Tensor, S: torch.Tensor, UO: torch.Tensor, SO: torch.Tensor,
                       target: torch.Tensor, v: torch.Tensor, v_out: torch.Tensor,
                       self_weight: Optional[torch.Tensor] = None, objective: str = "least_squares", lr: float = 0.01,

@@ -1088,3 +1088,10 @@ from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noq
 # weights, gt_push_csr.
 # ---------------------------------------------------------------------------
 from .gt import gt_csr, gt_csr_pm, gt_push_csr, gt_ring, separable_grad  # noqa: E402,F401
+
+# ---------------------------------------------------------------------------
+# EXTRA, the exact round that mixes the parameters only, on the agent-major
+# bank and ring (extra.py, on the validators above and gt.py's):
+# extra_csr, extra_ring, extra_ring_edges.
+# ---------------------------------------------------------------------------
+from .extra import extra_csr, extra_ring, extra_ring_edges  # noqa: E402,F401

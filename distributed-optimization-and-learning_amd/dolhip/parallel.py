@@ -35,6 +35,7 @@ import torch.distributed as dist
 
 from . import ops
 from .bank import device_matrix, row_stride
+from .parallel_extra import column_sharded_extra_step, sharded_ring_extra_step
 from .parallel_gt import column_sharded_gt_step
 
 # Fail fast instead of hanging: every collective of the engine's
@@ -244,6 +245,10 @@ class ShardedRing:
                           mom=m(n - 1, n), halo_prev=x[n - 2], halo_next=self.halo_next, P=P, n_rows=1, **kw)
         self.x, self.y = self.y, self.x
 
+    # extra_step(target, corr, self_w=None, **kw): one EXTRA round on the local block with
+    # dgd_step's halo schedule (only x has halos); corr in place; swaps x / y (parallel_extra.py)
+    extra_step = sharded_ring_extra_step
+
 
 def column_bounds(P: int, world: int, rank: int, align: int = 64) -> Tuple[int, int]:
     """Contiguous block [c0, c1) of the parameter dimension owned by `rank`, cut
@@ -317,6 +322,10 @@ class ColumnSharded:
     # gt_step(s, s_out, target, **kw): one gradient-tracking round on the rank's
     # column block; swaps x / y and returns the tracker pair swapped, (s_out, s)
     gt_step = column_sharded_gt_step
+
+    # extra_step(target, corr, **kw): one EXTRA round on the rank's column block
+    # (plan.apply_extra); corr in place; swaps x / y (parallel_extra.py)
+    extra_step = column_sharded_extra_step
 
     def gather(self, dst: int = 0, src: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
         """Full [N, P] on rank `dst` (checkpoints / tests; not on the round

@@ -478,6 +478,71 @@ int dol_gt_push_csr_f32(const float* U, int64_t ldu, const float* S, int64_t lds
                         int32_t objective, float lr, const float* v, float* v_out, hipStream_t s);
 
 /*
+ * One EXTRA round (Shi, Ling, Wu, Yin, "EXTRA: an exact first-order algorithm
+ * for decentralized consensus optimization", SIAM J. Optim. 25(2), 2015) of
+ * BASELINE config 3 on the agent-major bank with any sparse W in one pass.  With
+ * W~ = (I + W) / 2 the paper's recursion x(k+2) = (I + W) x(k+1) - W~ x(k) -
+ * lr [g(x(k+1)) - g(x(k))], x(1) = W x(0) - lr g(x(0)), is
+ *   x(k+1) = W x(k) - lr g(x(k)) - c(k);   c(k+1) = c(k) + (x(k) - W x(k)) / 2;   c(0) = 0
+ * so only X is mixed: the correction c is the agent's own row.  Not in the
+ * reference: it replaces the consensus + local step round of
+ * DIST/simulators.py:147-162 (a biased fixed point under a constant step size);
+ * the mix inside is its consensus (DIST/clients.py:61-69) in dol_mix_csr_f32's
+ * rounding.  X, Y (= x'), target and corr are row matrices of n rows; W = W_off
+ * + diag(self_w), W_off the square CSR (0 <= col < n, normally a zero diagonal),
+ * symmetric and doubly stochastic with a positive diagonal.  For every row i and
+ * column c, all fp32, each operation rounded once:
+ *   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e, product and sum rounded separately)
+ *   self_w != NULL:  ax = fl(ax + fl(self_w[i]*x_i))
+ *   r  = fl(x_i - ax)
+ *   x' = fl(fma(-lr, g(x_i, t_i), ax) - c_i)             g as dol_separable_grad_f32
+ *   c' = fma(0.5, r, c_i)                                written over c_i
+ * Start with corr = 0.  n < 0 or P < 0: DOL_EINVAL.  n == 0 or P == 0: DOL_OK,
+ * nothing launched.  No null pointers but self_w; ldx, ldy, ldt, ldc >= P;
+ * objective 0 or 1; Y distinct from X (a Jacobi mix); corr distinct from X, Y
+ * and target (it is updated in place); a launch above 2^24 blocks is refused as
+ * dol_mix_csr_f32 refuses it.  16-B columns where X, Y, target and corr are 16-B
+ * aligned with ld % 4 == 0, else scalar.  The round streams X (gathered), target
+ * and corr in and Y and corr out once: dol_dgd_csr_f32's five streams with
+ * momentum.  Stream-ordered; allocates nothing; does not synchronise.
+ */
+int dol_extra_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n, int64_t P, const int32_t* rowptr,
+                      const int32_t* col, const float* val, const float* self_w /* nullable */, const float* target,
+                      int64_t ldt, float* corr, int64_t ldc, int32_t objective, float lr, hipStream_t s);
+/*
+ * dol_extra_csr_f32's round (Shi, Ling, Wu, Yin 2015; not in the reference, in
+ * place of DIST/simulators.py:147-162 with the consensus of DIST/clients.py:61-69)
+ * on the agent-major ring, in dol_mix_ring_f32's layout and rounding: W = the
+ * ring stencil + diag(w_self).  For every row r and column c:
+ *   ax = fl(fl(+0 + fl(w_prev[r]*x[r-1])) + fl(w_next[r]*x[r+1]))
+ *   w_self != NULL:  ax = fl(ax + fl(w_self[r]*x[r]))
+ *   r_ = fl(x[r] - ax);  x' = fl(fma(-lr, g(x[r], t[r]), ax) - c[r]);  c' = fma(0.5, r_, c[r])
+ * the bits of dol_extra_csr_f32 on the ring's CSR with the same self weights.
+ * Row -1 / row n_rows of X are halo_prev / halo_next ([P] each; both or
+ * neither), or the wrap-around rows of X itself without halos (n_rows >= 3
+ * then; with halos n_rows >= 1).  Only X has halos: corr and target are the
+ * block's own rows.  Other argument rules as dol_extra_csr_f32; 16-B columns
+ * also need 16-B aligned halos.
+ */
+int dol_extra_ring_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n_rows, int64_t P,
+                       const float* halo_prev, const float* halo_next, const float* w_prev, const float* w_next,
+                       const float* w_self /* nullable */, const float* target, int64_t ldt, float* corr, int64_t ldc,
+                       int32_t objective, float lr, hipStream_t s);
+/*
+ * Rows 0 and n_rows - 1 of dol_extra_ring_f32 with halos, in one launch (see
+ * dol_mix_ring_edges_f32; Shi, Ling, Wu, Yin 2015; not in the reference, in
+ * place of DIST/simulators.py:147-162 / DIST/clients.py:61-69): the second half
+ * of a sharded ring's EXTRA round.  Both halos are required; w_prev, w_next,
+ * w_self, target and corr are the whole block's ([n_rows] / n_rows rows), of
+ * which rows 0 and n_rows - 1 are read (and, corr, written).  Other argument
+ * rules as dol_extra_ring_f32.
+ */
+int dol_extra_ring_edges_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n_rows, int64_t P,
+                             const float* halo_prev, const float* halo_next, const float* w_prev,
+                             const float* w_next, const float* w_self /* nullable */, const float* target,
+                             int64_t ldt, float* corr, int64_t ldc, int32_t objective, float lr, hipStream_t s);
+
+/*
  * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the
  * separable losses of dol_dgd_ring_f32 (objective 0: fl(x - t), 1:
  * -t / (1 + exp(t x)), the same device code).  Elementwise, so it serves the

@@ -9,7 +9,11 @@ gt_ring_dma_kernel (the objective is its second template argument), L = csr
 gt_csr_xcd_kernel (the pinned tiles: every f4 column at P = 2^20; its third),
 L = csr-push gt_push_csr_xcd_kernel (the same tiles; the program after `--` is
 then `python tools/gt_push_ab.py --legs a ...`; the n-float v' kernel and the
-2 n floats of v the main kernel reads are not counted),
+2 n floats of v the main kernel reads are not counted), L = extra-csr /
+extra-ring the EXTRA round's instantiations of the mixing kernels themselves,
+csr_xcd_kernel<32, 2, ExtraEpi<OBJ, SELF>> and ring_mix_dma_kernel<4,
+ExtraEpi<OBJ, SELF>, ...> (the program after `--` is then `python
+tools/extra_ab.py --legs a ...` or `--legs e ...`; the same five streams),
 against the algorithmic 3 N P 4 read and 2 N P 4 written.  FETCH_SIZE counts
 half the bytes of a wide streaming read on gfx950, so `read_over_algorithmic`
 doubles it."""
@@ -23,7 +27,9 @@ import statistics
 
 # the measured kernel's demangled name up to its objective, the one group
 KERNELS = {"ring": r"gt_ring_dma_kernel<\d+, (\d+)", "csr": r"gt_csr_xcd_kernel<\d+, \d+, (\d+)",
-           "csr-push": r"gt_push_csr_xcd_kernel<\d+, \d+, (\d+)"}
+           "csr-push": r"gt_push_csr_xcd_kernel<\d+, \d+, (\d+)",
+           "extra-csr": r"csr_xcd_kernel<\d+, \d+, [^<]*ExtraEpi<(\d+)",
+           "extra-ring": r"ring_mix_dma_kernel<\d+, [^<]*ExtraEpi<(\d+)"}
 
 
 def main():
