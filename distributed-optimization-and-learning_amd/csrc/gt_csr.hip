@@ -1,14 +1,19 @@
-// gt_csr.hip — one gradient-tracking round (DIGing / NEXT) on the agent-major
-// bank with any sparse W in one HBM pass: dol_gt_csr_f32, the sibling of
-// dol_gt_ring_f32 (gt_ring.hip, rings only) and of dol_gt_csr_pm_f32
-// (pmajor.hip, at most 4096 agents).  Its own translation unit, so csr.o,
-// gt_ring.o and their pinned kernels stay as they are.
+// gt_csr.hip — one gradient-tracking round on the agent-major bank with any
+// sparse weight matrix in one HBM pass, in two forms that share every kernel:
+//   dol_gt_csr_f32       DIGing / NEXT with a doubly stochastic W, the sibling
+//                        of dol_gt_ring_f32 (gt_ring.hip, rings only) and of
+//                        dol_gt_csr_pm_f32 (pmajor.hip, at most 4096 agents);
+//   dol_gt_push_csr_f32  push-sum gradient tracking (ADD-OPT, Xi-Xin-Khan 2018;
+//                        Push-DIGing in combine-then-adapt form) with a
+//                        column-stochastic C, for weights that are not doubly
+//                        stochastic.
 //
 // Layout as csr.hip: agent i's vector is row i of a row-major fp32 matrix.  Two
-// row matrices, the parameters X and the trackers S, are gathered through ONE
-// read of rowptr / col / val per row; the centre rows x_i, s_i and the target
-// row t_i ride along.  For every row i and column c, all fp32, each operation
-// rounded once (-ffp-contract=off):
+// row matrices, the parameters X (the push-sum numerators U of the push-sum
+// round) and the trackers S, are gathered through ONE read of rowptr / col /
+// val per row; the centre rows x_i, s_i and the target row t_i ride along.  For
+// every row i and column c, all fp32, each operation rounded once
+// (-ffp-contract=off):
 //   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e: fmac())     as = the same over s
 // and then gt_finish (dol_launch.h) with d = self_w[i], the lane that
 // dol_gt_csr_pm_f32 and dol_gt_ring_f32 run too: the same bits as the first on
@@ -16,6 +21,33 @@
 // csr_xcd_kernel / csr_mix_kernel cannot say this: an epilogue sees one mixed
 // value, this round needs two mixes through one index and the centre rows of
 // both (gt_ring.hip's header, for the ring).
+//
+// The push-sum round: C = C_off + diag(self_w), C_off the CSR whose row i lists
+// i's in-neighbours.  Beside the two mixes above (x = u),
+//   av = sum_e val[e] * v[col[e]]      (the same rounding, on the n-vector v)
+//   av = fl(av + fl(d_i v_i)) with self weights;   v'_i = av
+// and then gt_push_finish (dol_launch.h) with d = self_w[i], v = v[i], av =
+// v'[i]: the gradients are taken at z = u / v and z' = u' / av, two correctly
+// rounded divisions per coordinate.  z is not stored (it is U / v), so the
+// round moves the five streams of dol_gt_csr_f32 plus 2 n floats.
+// How v' is produced: gt_push_v_kernel (n threads) runs first in the same call
+// and writes v_out; the main kernels, ordered after it on the stream, read
+// v[i] and v_out[i] as two per-row scalars.  The degree-4 fast path's register
+// budget is the reason: the mix of v inside the main kernels would add a third
+// gather to it.
+//
+// One kernel body for both rounds.  gt_csr_kernel and gt_csr_xcd_kernel take
+// the round as their first template parameter, a tag (GtPlain, GtPushSum) that
+// names the per-row scalars (Row, load) and the lane (finish); geometry,
+// policies and clamped ragged rows are the same text for both.  Two rules keep
+// the emitted code what it was when each round had kernels of its own:
+//   * the tag stays stateless: a type, never an object passed to the kernel;
+//   * v and vnew stay `const float* __restrict__` kernel parameters (two null
+//     pointers that are never read in the plain round).
+// Carried as __restrict__ members of a policy object passed by value they lose
+// their alias information: the f4 small-n push-sum kernels went from 78 / 80
+// VGPRs to 82 / 84 and from 6 waves per SIMD to 5, the scalar ones from 40 to
+// 42 (the pinned kernels were unaffected).
 //
 // Policies: the gathered rows and the centre rows load with the default policy
 // (a centre row is some other row's neighbour); the target row is read once and
@@ -45,16 +77,31 @@
 // a third of the re-reads miss at 1024 agents (1 MiB of slabs per tile) was
 // not found.  Not measured:
 // other rows-per-block counts (csr.hip's PASSES finding is taken over), 384-B
-// tiles (they lost on the mix), an LDS-staged gather.
+// tiles (they lost on the mix), an LDS-staged gather.  (All of the above is the
+// plain round's; not measured again for the push-sum round, nor when the two
+// rounds were given one body.)
 // Degree-4 fast path: all indices, then all 16 neighbour f4s of both matrices
 // and the 6 centre / target f4s in flight per thread: 112-122 VGPRs, no scratch,
 // 4 waves per SIMD.
+//
+// Resource usage, from the compiler's kernel-resource-usage remarks (gfx950,
+// -O3; occupancy in waves per SIMD; no instantiation uses scratch or LDS):
+//   kernel                                  VGPRs: LS / LS+self / logistic / logistic+self   scratch   occupancy
+//   gt_csr_xcd_kernel<GtPlain, 32, 2>       112 / 122 / 115 / 119                            0         4
+//   gt_csr_kernel<GtPlain, f4>              78 / 78 / 80 / 80                                0         6
+//   gt_csr_kernel<GtPlain, float>           40 / 40 / 40 / 40                                0         8
+//   gt_csr_xcd_kernel<GtPushSum, 32, 2>     118 / 119 / 126 / 122                            0         4
+//   gt_csr_kernel<GtPushSum, f4>            78 / 78 / 80 / 80                                0         6
+//   gt_csr_kernel<GtPushSum, float>         40 / 40 / 40 / 40                                0         8
+//   gt_push_v_kernel                        12 (with and without self weights)               0         8
+// The pinned push-sum kernel keeps the plain one's 4 waves per SIMD (128 VGPRs):
+// the two per-row scalars and the divisions' temporaries fit beside its 112-122.
 #include "dol_launch.h"
 
 namespace {
 constexpr int kThreads = 256;  // 4 waves of 64
-constexpr int kGtCsrRows = 16;  // rows per block of gt_csr_kernel (csr.hip's RPB)
-constexpr int kGtCsrMinXcdRows = 512;  // the XCD-pinned form from this many rows (csr.hip's rule)
+constexpr int kRows = 16;  // rows per block of gt_csr_kernel (csr.hip's RPB)
+constexpr int kMinXcdRows = 512;  // the XCD-pinned form from this many rows (csr.hip's rule)
 
 struct GtCsr {
   const float* X; int64_t ldx;
@@ -64,29 +111,71 @@ struct GtCsr {
   const float* T; int64_t ldt;
   float neg_lr;
 };
-// (rowptr, col, val and the self weights are kernel arguments of their own,
-// const __restrict__, as in csr.hip and gt_ring.hip)
+// (rowptr, col, val, the self weights and the two push-sum weight vectors are
+// kernel arguments of their own, const __restrict__, as in csr.hip and
+// gt_ring.hip)
+
+// The round tags.  Row: what a row carries beside its self weight; load(): read
+// it at row r; finish(): the lane of dol_launch.h.
+struct GtPlain {
+  struct Row {};
+  static __device__ __forceinline__ Row load(const float*, const float*, int64_t) { return {}; }
+  template <int OBJ, bool SELF, typename V>
+  static __device__ __forceinline__ void finish(V ax, V as, V x, V s, V t, float d, float neg_lr, Row, V& xo, V& so) {
+    gt_finish<OBJ>(ax, as, x, s, t, d, SELF, neg_lr, xo, so);
+  }
+};
+struct GtPushSum {
+  struct Row { float v, av; };  // the agent's push-sum weight before the round and after it
+  static __device__ __forceinline__ Row load(const float* __restrict__ v, const float* __restrict__ vnew, int64_t r) {
+    return {v[r], vnew[r]};
+  }
+  template <int OBJ, bool SELF, typename V>
+  static __device__ __forceinline__ void finish(V au, V as, V u, V s, V t, float d, float neg_lr, Row w, V& uo, V& so) {
+    gt_push_finish<OBJ>(au, as, u, s, t, d, SELF, neg_lr, w.v, w.av, uo, so);
+  }
+};
+
+// ----------------------------------------------------------------------------
+// v' = C v, one thread per agent: the mix's rounding on a vector.
+// ----------------------------------------------------------------------------
+template <bool SELF>
+__global__ __launch_bounds__(kThreads) void gt_push_v_kernel(int n_rows, const int32_t* __restrict__ rowptr,
+                                                             const int32_t* __restrict__ col,
+                                                             const float* __restrict__ val,
+                                                             const float* __restrict__ wself,
+                                                             const float* __restrict__ v, float* __restrict__ vout) {
+  const int64_t r = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (r >= n_rows) return;
+  const int e1 = rowptr[r + 1];
+  float av = 0.0f;
+  for (int e = rowptr[r]; e < e1; ++e) av = fmac(av, val[e], v[col[e]]);
+  if (SELF) av = av + wself[r] * v[r];
+  vout[r] = av;
+}
 
 // ----------------------------------------------------------------------------
 // 4 KiB column tiles (V = f4: 256 lanes x 16 B) or 1 KiB of scalar columns (V =
 // float: the P % 4 tail, or every column when a row base is not 16-B aligned),
-// kGtCsrRows rows per block, row group fastest as csr_mix_kernel: small graphs,
-// and the f4 columns the pinned tiles leave over.  c_off: the first element
-// column of this launch.
+// kRows rows per block, row group fastest as csr_mix_kernel: small graphs, and
+// the f4 columns the pinned tiles leave over.  c_off: the first element column
+// of this launch.
 // ----------------------------------------------------------------------------
-template <typename V, int OBJ, bool SELF>
+template <class R, typename V, int OBJ, bool SELF>
 __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, int64_t c_off, int64_t ncols_v,
                                                           int64_t n_row_groups, const int32_t* __restrict__ rowptr,
                                                           const int32_t* __restrict__ col,
                                                           const float* __restrict__ val,
-                                                          const float* __restrict__ wself) {
+                                                          const float* __restrict__ wself,
+                                                          const float* __restrict__ v,
+                                                          const float* __restrict__ vnew) {
   constexpr int VW = Vec<V>::W;
   const int64_t b = blockIdx.x;
   const int rg = static_cast<int>(b % n_row_groups);
   const int64_t c = (b / n_row_groups) * kThreads + threadIdx.x;
   if (c >= ncols_v) return;
-  const int r0 = rg * kGtCsrRows;
-  const int r1 = min(r0 + kGtCsrRows, n_rows);
+  const int r0 = rg * kRows;
+  const int r1 = min(r0 + kRows, n_rows);
   const int64_t cf = c_off + c * VW;  // element column
   const float* xb = a.X + cf;
   const float* sb = a.S + cf;
@@ -96,6 +185,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, i
     const V t = ldv<V, sizeof(V) == 16>(reinterpret_cast<const V*>(a.T + int64_t(r) * a.ldt + cf));
     const V xc = xat(r), sc = sat(r);
     const float ws = SELF ? wself[r] : 0.0f;
+    const typename R::Row row = R::load(v, vnew, r);
     const int e0 = rowptr[r];
     const int e1 = rowptr[r + 1];
     V ax = vzero(V{}), as = vzero(V{});
@@ -104,24 +194,24 @@ __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, i
       const int64_t c0 = col[e], c1 = col[e + 1], c2 = col[e + 2], c3 = col[e + 3];
       const V x0 = xat(c0), x1 = xat(c1), x2 = xat(c2), x3 = xat(c3);
       const V s0 = sat(c0), s1 = sat(c1), s2 = sat(c2), s3 = sat(c3);
-      const float v0 = val[e], v1 = val[e + 1], v2 = val[e + 2], v3 = val[e + 3];
-      ax = fmac(ax, v0, x0);
-      as = fmac(as, v0, s0);
-      ax = fmac(ax, v1, x1);
-      as = fmac(as, v1, s1);
-      ax = fmac(ax, v2, x2);
-      as = fmac(as, v2, s2);
-      ax = fmac(ax, v3, x3);
-      as = fmac(as, v3, s3);
+      const float w0 = val[e], w1 = val[e + 1], w2 = val[e + 2], w3 = val[e + 3];
+      ax = fmac(ax, w0, x0);
+      as = fmac(as, w0, s0);
+      ax = fmac(ax, w1, x1);
+      as = fmac(as, w1, s1);
+      ax = fmac(ax, w2, x2);
+      as = fmac(as, w2, s2);
+      ax = fmac(ax, w3, x3);
+      as = fmac(as, w3, s3);
     }
     for (; e < e1; ++e) {
       const int64_t cj = col[e];
-      const float v = val[e];
-      ax = fmac(ax, v, xat(cj));
-      as = fmac(as, v, sat(cj));
+      const float w = val[e];
+      ax = fmac(ax, w, xat(cj));
+      as = fmac(as, w, sat(cj));
     }
     V xo, so;
-    gt_finish<OBJ>(ax, as, xc, sc, t, ws, SELF, a.neg_lr, xo, so);
+    R::template finish<OBJ, SELF>(ax, as, xc, sc, t, ws, a.neg_lr, row, xo, so);
     __builtin_nontemporal_store(xo, reinterpret_cast<V*>(a.XO + int64_t(r) * a.ldxo + cf));
     __builtin_nontemporal_store(so, reinterpret_cast<V*>(a.SO + int64_t(r) * a.ldso + cf));
   }
@@ -137,15 +227,17 @@ __global__ __launch_bounds__(kThreads) void gt_csr_kernel(GtCsr a, int n_rows, i
 // Degree-4 rows (random-regular) gather every pass's indices, then every
 // neighbour row of both matrices, then the centre and target rows, before any
 // arithmetic; other degrees walk their lists 4 at a time.  Rows past the end
-// of a ragged block read row n - 1's lists and rows (valid loads) and store
-// nothing.
+// of a ragged block read row n - 1's lists, rows and push-sum weights (valid
+// loads) and store nothing.
 // ----------------------------------------------------------------------------
-template <int W, int PASSES, int OBJ, bool SELF>
+template <class R, int W, int PASSES, int OBJ, bool SELF>
 __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_rows, uint32_t nrb, uint32_t ntiles,
                                                               const int32_t* __restrict__ rowptr,
                                                               const int32_t* __restrict__ col,
                                                               const float* __restrict__ val,
-                                                              const float* __restrict__ wself) {
+                                                              const float* __restrict__ wself,
+                                                              const float* __restrict__ v,
+                                                              const float* __restrict__ vnew) {
   constexpr int ROWS = kThreads / W;
   constexpr int RB = ROWS * PASSES;
   const uint32_t b = blockIdx.x;
@@ -169,16 +261,19 @@ __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_row
     e1[p] = rowptr[rc[p] + 1];
     four = four && (e1[p] - e0[p] == 4);
   }
-  // the centre rows, the target row and the self weight of every pass: issued
-  // ahead of the gathers on either path (clamped rows: valid loads)
+  // the centre rows, the target row, the self weight and the round's own row
+  // scalars of every pass: issued ahead of the gathers on either path (clamped
+  // rows: valid loads)
   f4 xc[PASSES], sc[PASSES], tv[PASSES];
   float ws[PASSES];
+  typename R::Row row[PASSES];
 #pragma unroll
   for (int p = 0; p < PASSES; ++p) {
     xc[p] = xb[int64_t(rc[p]) * ldxv];
     sc[p] = sb[int64_t(rc[p]) * ldsv];
     tv[p] = __builtin_nontemporal_load(tb + int64_t(rc[p]) * ldtv);
     ws[p] = SELF ? wself[rc[p]] : 0.0f;
+    row[p] = R::load(v, vnew, rc[p]);
   }
   if (four) {
     int cc[PASSES][4];
@@ -208,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_row
           as = fmac(as, vv[p][q], ss[p][q]);
         }
         f4 xo, so;
-        gt_finish<OBJ>(ax, as, xc[p], sc[p], tv[p], ws[p], SELF, a.neg_lr, xo, so);
+        R::template finish<OBJ, SELF>(ax, as, xc[p], sc[p], tv[p], ws[p], a.neg_lr, row[p], xo, so);
         __builtin_nontemporal_store(xo, reinterpret_cast<f4*>(a.XO + int64_t(rr[p]) * a.ldxo) + c);
         __builtin_nontemporal_store(so, reinterpret_cast<f4*>(a.SO + int64_t(rr[p]) * a.ldso) + c);
       }
@@ -225,36 +320,71 @@ __global__ __launch_bounds__(kThreads) void gt_csr_xcd_kernel(GtCsr a, int n_row
         const int64_t c0 = col[e], c1 = col[e + 1], c2 = col[e + 2], c3 = col[e + 3];
         const f4 x0 = xb[c0 * ldxv], x1 = xb[c1 * ldxv], x2 = xb[c2 * ldxv], x3 = xb[c3 * ldxv];
         const f4 s0 = sb[c0 * ldsv], s1 = sb[c1 * ldsv], s2 = sb[c2 * ldsv], s3 = sb[c3 * ldsv];
-        const float v0 = val[e], v1 = val[e + 1], v2 = val[e + 2], v3 = val[e + 3];
-        ax = fmac(ax, v0, x0);
-        as = fmac(as, v0, s0);
-        ax = fmac(ax, v1, x1);
-        as = fmac(as, v1, s1);
-        ax = fmac(ax, v2, x2);
-        as = fmac(as, v2, s2);
-        ax = fmac(ax, v3, x3);
-        as = fmac(as, v3, s3);
+        const float w0 = val[e], w1 = val[e + 1], w2 = val[e + 2], w3 = val[e + 3];
+        ax = fmac(ax, w0, x0);
+        as = fmac(as, w0, s0);
+        ax = fmac(ax, w1, x1);
+        as = fmac(as, w1, s1);
+        ax = fmac(ax, w2, x2);
+        as = fmac(as, w2, s2);
+        ax = fmac(ax, w3, x3);
+        as = fmac(as, w3, s3);
       }
       for (; e < e1[p]; ++e) {
         const int64_t cj = col[e];
-        const float v = val[e];
-        ax = fmac(ax, v, xb[cj * ldxv]);
-        as = fmac(as, v, sb[cj * ldsv]);
+        const float w = val[e];
+        ax = fmac(ax, w, xb[cj * ldxv]);
+        as = fmac(as, w, sb[cj * ldsv]);
       }
       f4 xo, so;
-      gt_finish<OBJ>(ax, as, xc[p], sc[p], tv[p], ws[p], SELF, a.neg_lr, xo, so);
+      R::template finish<OBJ, SELF>(ax, as, xc[p], sc[p], tv[p], ws[p], a.neg_lr, row[p], xo, so);
       __builtin_nontemporal_store(xo, reinterpret_cast<f4*>(a.XO + int64_t(r) * a.ldxo) + c);
       __builtin_nontemporal_store(so, reinterpret_cast<f4*>(a.SO + int64_t(r) * a.ldso) + c);
     }
   }
 }
 
-template <typename V, int OBJ, bool SELF>
+template <class R, typename V, int OBJ, bool SELF>
 void launch_gt_csr(const GtCsr& a, int n_rows, int64_t c_off, int64_t ncols_v, const int32_t* rowptr,
-                   const int32_t* col, const float* val, const float* wself, hipStream_t s) {
-  const int64_t n_rg = cdiv(n_rows, kGtCsrRows);
-  hipLaunchKernelGGL((gt_csr_kernel<V, OBJ, SELF>), dim3(static_cast<unsigned>(cdiv(ncols_v, kThreads) * n_rg)),
-                     dim3(kThreads), 0, s, a, n_rows, c_off, ncols_v, n_rg, rowptr, col, val, wself);
+                   const int32_t* col, const float* val, const float* wself, const float* v, const float* vnew,
+                   hipStream_t s) {
+  const int64_t n_rg = cdiv(n_rows, kRows);
+  hipLaunchKernelGGL((gt_csr_kernel<R, V, OBJ, SELF>), dim3(static_cast<unsigned>(cdiv(ncols_v, kThreads) * n_rg)),
+                     dim3(kThreads), 0, s, a, n_rows, c_off, ncols_v, n_rg, rowptr, col, val, wself, v, vnew);
+}
+
+// What both entry points do once their own argument rules have passed: the
+// column split, the launch-size rules, the XCD decision and the launches.
+// first(self): the round's own launch ahead of the main kernels (v' = C v).
+template <class R, class First>
+int gt_csr_round(const char* nm, const GtRows& m, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                 const float* val, const float* self_w, int32_t objective, float lr, const float* v,
+                 const float* vnew, hipStream_t s, First first) {
+  const ColSplit cs = split_cols(P, m.vec_ok());
+  constexpr int XW = 32, XPASSES = 2;  // XCD-pinned tiles: 512 B of a row, 16 rows per block
+  const int64_t n_rg = cdiv(n, kRows);
+  if (mul_sat(cdiv(cs.n4, kThreads), n_rg) > kMaxBlocks || mul_sat(cdiv(cs.tail, kThreads), n_rg) > kMaxBlocks)
+    return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+  const bool use_xcd = cs.n4 >= XW && n >= kMinXcdRows;
+  const int64_t nt = use_xcd ? cs.n4 / XW : 0;
+  const int64_t nrb = cdiv(n, (kThreads / XW) * XPASSES);
+  if (cdiv(nt, 8) * 8 * nrb > kMaxBlocks * 8) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+  const int64_t done4 = nt * XW;
+  const GtCsr a{m.X, m.ldx, m.S, m.lds, m.XO, m.ldxo, m.SO, m.ldso, m.T, m.ldt, -lr};
+  dispatch([&](auto obj, auto self) {
+    constexpr int OBJ = decltype(obj)::value;
+    constexpr bool SELF = decltype(self)::value;
+    first(self);
+    if (nt > 0)
+      hipLaunchKernelGGL((gt_csr_xcd_kernel<R, XW, XPASSES, OBJ, SELF>),
+                         dim3(static_cast<unsigned>(cdiv(nt, 8) * 8 * nrb)), dim3(kThreads), 0, s, a, n,
+                         static_cast<uint32_t>(nrb), static_cast<uint32_t>(nt), rowptr, col, val, self_w, v, vnew);
+    if (cs.n4 > done4)
+      launch_gt_csr<R, f4, OBJ, SELF>(a, n, done4 * 4, cs.n4 - done4, rowptr, col, val, self_w, v, vnew, s);
+    if (cs.tail > 0)
+      launch_gt_csr<R, float, OBJ, SELF>(a, n, cs.n4 * 4, cs.tail, rowptr, col, val, self_w, v, vnew, s);
+  }, Ints<0, 1>{objective}, Bool{self_w != nullptr});
+  return check_launch(nm);
 }
 
 }  // namespace
@@ -269,29 +399,23 @@ int dol_gt_csr_f32(const float* X, int64_t ldx, const float* S, int64_t lds, flo
   const GtRows m{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt};
   DOL_CHECKED(m.check(nm, n, P, !rowptr || !col || !val));
   if (const int rc = GtRows::objective_ok(nm, objective)) return rc;
-  const ColSplit cs = split_cols(P, m.vec_ok());
-  constexpr int XW = 32, XPASSES = 2;  // XCD-pinned tiles: 512 B of a row, 16 rows per block
-  const int64_t n_rg = cdiv(n, kGtCsrRows);
-  if (mul_sat(cdiv(cs.n4, kThreads), n_rg) > kMaxBlocks || mul_sat(cdiv(cs.tail, kThreads), n_rg) > kMaxBlocks)
-    return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
-  const bool use_xcd = cs.n4 >= XW && n >= kGtCsrMinXcdRows;
-  const int64_t nt = use_xcd ? cs.n4 / XW : 0;
-  const int64_t nrb = cdiv(n, (kThreads / XW) * XPASSES);
-  if (cdiv(nt, 8) * 8 * nrb > kMaxBlocks * 8) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
-  const int64_t done4 = nt * XW;
-  const GtCsr a{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt, -lr};
-  dispatch([&](auto obj, auto self) {
-    constexpr int OBJ = decltype(obj)::value;
-    constexpr bool SELF = decltype(self)::value;
-    if (nt > 0)
-      hipLaunchKernelGGL((gt_csr_xcd_kernel<XW, XPASSES, OBJ, SELF>),
-                         dim3(static_cast<unsigned>(cdiv(nt, 8) * 8 * nrb)), dim3(kThreads), 0, s, a, n,
-                         static_cast<uint32_t>(nrb), static_cast<uint32_t>(nt), rowptr, col, val, self_w);
-    if (cs.n4 > done4)
-      launch_gt_csr<f4, OBJ, SELF>(a, n, done4 * 4, cs.n4 - done4, rowptr, col, val, self_w, s);
-    if (cs.tail > 0) launch_gt_csr<float, OBJ, SELF>(a, n, cs.n4 * 4, cs.tail, rowptr, col, val, self_w, s);
-  }, Ints<0, 1>{objective}, Bool{self_w != nullptr});
-  return check_launch(nm);
+  return gt_csr_round<GtPlain>(nm, m, n, P, rowptr, col, val, self_w, objective, lr, nullptr, nullptr, s, [](auto) {});
+}
+
+int dol_gt_push_csr_f32(const float* U, int64_t ldu, const float* S, int64_t lds, float* UO, int64_t lduo, float* SO,
+                        int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                        const float* val, const float* self_w, const float* target, int64_t ldt, int32_t objective,
+                        float lr, const float* v, float* v_out, hipStream_t s) {
+  const char* nm = "dol_gt_push_csr_f32";
+  const GtRows m{U, ldu, S, lds, UO, lduo, SO, ldso, target, ldt};
+  DOL_CHECKED(m.check(nm, n, P, !rowptr || !col || !val || !v || !v_out));
+  if (const int rc = GtRows::objective_ok(nm, objective)) return rc;
+  if (v == v_out) return fail(DOL_EINVAL, "%s: v and v_out alias (every v' reads its neighbours' v)", nm);
+  // v' = C v first: the main kernels read it, ordered after it on the stream
+  return gt_csr_round<GtPushSum>(nm, m, n, P, rowptr, col, val, self_w, objective, lr, v, v_out, s, [&](auto self) {
+    hipLaunchKernelGGL((gt_push_v_kernel<decltype(self)::value>), dim3(static_cast<unsigned>(cdiv(n, kThreads))),
+                       dim3(kThreads), 0, s, n, rowptr, col, val, self_w, v, v_out);
+  });
 }
 
 }  // extern "C"

@@ -139,6 +139,29 @@ def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor
     return XO, SO
 
 
+def _csr_round_args(name: str, state, rowptr, col, val, target, self_weight, objective, lr, P, vectors=(),
+                    then=None) -> tuple:
+    """The rules gt_csr and gt_push_csr share, in the order they fire, and the
+    arguments their native calls start with (everything up to lr).  state: the
+    four (name, matrix) pairs; vectors: the op's own (name, n floats) pairs,
+    checked ahead of self_weight; then(): the op's own rule on them."""
+    obj = _check_objective(name, objective)
+    n = rowptr.shape[0] - 1
+    _distinct_state(name, state)
+    X = state[0][1]
+    for nm, w in tuple(vectors) + ((("self_weight", self_weight),) if self_weight is not None else ()):
+        _ops._check_array(nm, w, torch.float32, n, X.device)
+    if then is not None:
+        then()
+    P = X.shape[1] if P is None else P
+    lds = _leading_dims(state, ("target", target), P, n)
+    _ops._check_csr(rowptr, col, val, X.device, same_length=False)
+    _check_square(rowptr, col, n)
+    rows = tuple(a for (_, t), ld in zip(state, lds) for a in (t.data_ptr(), ld))
+    return rows + (n, P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
+                   _ops._ptr(self_weight), target.data_ptr(), lds[4], obj, float(lr))
+
+
 def gt_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, rowptr: torch.Tensor,
            col: torch.Tensor, val: torch.Tensor, target: torch.Tensor, self_weight: Optional[torch.Tensor] = None,
            objective: str = "least_squares", lr: float = 0.01,
@@ -155,19 +178,9 @@ def gt_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor,
     rules of this op: a known objective; the four state matrices distinct (a
     Jacobi update of both); a self-weight vector of n floats; a square W.
     Returns (XO, SO)."""
-    obj = _check_objective("gt_csr", objective)
-    n = rowptr.shape[0] - 1
-    state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
-    _distinct_state("gt_csr", state)
-    if self_weight is not None:
-        _ops._check_array("self_weight", self_weight, torch.float32, n, X.device)
-    P = X.shape[1] if P is None else P
-    ldx, ld_s, ldxo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
-    _ops._check_csr(rowptr, col, val, X.device, same_length=False)
-    _check_square(rowptr, col, n)
-    _native.call("dol_gt_csr_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,
-                 P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
-                 _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
+    call = _csr_round_args("gt_csr", (("X", X), ("S", S), ("XO", XO), ("SO", SO)), rowptr, col, val, target,
+                           self_weight, objective, lr, P)
+    _native.call("dol_gt_csr_f32", *call, _ops._stream(X))
     return XO, SO
 
 
@@ -197,22 +210,13 @@ def gt_push_csr(U: torch.Tensor, S: torch.Tensor, UO: torch.Tensor, SO: torch.Te
     n floats; a square C) and: v and v_out are n float32 values on the device,
     and distinct.  Values are not checked: a zero v_i divides like IEEE.
     Returns (UO, SO, v_out)."""
-    obj = _check_objective("gt_push_csr", objective)
-    n = rowptr.shape[0] - 1
-    state = (("U", U), ("S", S), ("UO", UO), ("SO", SO))
-    _distinct_state("gt_push_csr", state)
-    for nm, w in (("v", v), ("v_out", v_out)) + ((("self_weight", self_weight),) if self_weight is not None else ()):
-        _ops._check_array(nm, w, torch.float32, n, U.device)
-    if v is v_out or v.data_ptr() == v_out.data_ptr():
-        raise ValueError("gt_push_csr: v and v_out alias: every v' reads its neighbours' v")
-    P = U.shape[1] if P is None else P
-    ldu, ld_s, lduo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
-    _ops._check_csr(rowptr, col, val, U.device, same_length=False)
-    _check_square(rowptr, col, n)
-    _native.call("dol_gt_push_csr_f32", U.data_ptr(), ldu, S.data_ptr(), ld_s, UO.data_ptr(), lduo, SO.data_ptr(), ldso,
-                 n, P, rowptr.data_ptr(), _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val),
-                 _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), v.data_ptr(), v_out.data_ptr(),
-                 _ops._stream(U))
+    def distinct_v():
+        if v is v_out or v.data_ptr() == v_out.data_ptr():
+            raise ValueError("gt_push_csr: v and v_out alias: every v' reads its neighbours' v")
+
+    call = _csr_round_args("gt_push_csr", (("U", U), ("S", S), ("UO", UO), ("SO", SO)), rowptr, col, val, target,
+                           self_weight, objective, lr, P, vectors=(("v", v), ("v_out", v_out)), then=distinct_v)
+    _native.call("dol_gt_push_csr_f32", *call, v.data_ptr(), v_out.data_ptr(), _ops._stream(U))
     return UO, SO, v_out
 
 

@@ -781,6 +781,8 @@ class SeparableGTCSR:
     is another element order: SeparableGTPM.from_agent_major makes the same
     problem there."""
 
+    _IN, _OUT = "x", "y"  # the bank's names for the parameters in and out
+
     def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
                  self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
         from . import ops
@@ -791,10 +793,10 @@ class SeparableGTCSR:
         self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
         self.bank = bank if bank is not None else AgentBank(self.N, P, dev)
         self.P = self.bank.P
-        _seeded_draw(self.bank.buffer("x"), self.bank.buffer("target"), objective, seed, dev)
-        for name in ("y", "s", "s_out"):
+        _seeded_draw(self.bank.buffer(self._IN), self.bank.buffer("target"), objective, seed, dev)
+        for name in (self._OUT, "s", "s_out"):
             self.bank.buffer(name, zero=True)
-        ops.separable_grad(self.bank.rows("x"), self.bank.rows("target"), self.bank.rows("s"), objective)
+        ops.separable_grad(self.bank.rows(self._IN), self.bank.rows("target"), self.bank.rows("s"), objective)
         self.rounds = 0
 
     @staticmethod
@@ -812,7 +814,7 @@ class SeparableGTCSR:
         self.rounds += 1
 
     def params(self) -> torch.Tensor:
-        return self.bank.rows("x")
+        return self.bank.rows(self._IN)
 
     def tracker(self) -> torch.Tensor:
         return self.bank.rows("s")
@@ -850,7 +852,7 @@ class SeparableGT(SeparableGTCSR):
                              f"sparse W of up to {ops.GT_MAX_AGENTS} agents")
 
 
-class SeparableGTPush:
+class SeparableGTPush(SeparableGTCSR):
     """Config 3 with push-sum gradient tracking (ADD-OPT / Push-DIGing) on the
     agent-major bank: SeparableGTCSR's sibling for weights that are
     column-stochastic only, one call and one pass over U, S and the targets per
@@ -868,28 +870,22 @@ class SeparableGTPush:
     (trackers) and target, with SeparableDGD's seeded init (u starts as x(0));
     v / v_out are the push-sum weights, n floats each, starting at 1; s starts
     as ops.separable_grad(x(0), target).  The estimate every agent holds is
-    params() = u / v."""
+    params() = u / v.  Bank set-up, tracker start and the other accessors are
+    SeparableGTCSR's, on u / u_out."""
+
+    _IN, _OUT = "u", "u_out"
 
     def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
                  self_weight=None, seed: int = 2028, bank: Optional[AgentBank] = None):
-        from . import ops
-        if plan.kind == "dense":
-            raise ValueError("the gradient-tracking round mixes a sparse (CSR) W")
+        super().__init__(plan, P, objective, lr, self_weight, seed, bank)
+        self.v = torch.ones(self.N, dtype=torch.float32, device=plan.device)
+        self.v_out = torch.ones(self.N, dtype=torch.float32, device=plan.device)
+
+    @staticmethod
+    def _check_plan(plan) -> None:
+        SeparableGTCSR._check_plan(plan)
         if plan.kind == "ring":
             raise ValueError("SeparableGTPush runs on a CSR plan (got kind 'ring'); build it with allow_ring=False")
-        self.plan, self.objective, self.lr = plan, objective, float(lr)
-        self.N = plan.n_rows
-        dev = plan.device
-        self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
-        self.bank = bank if bank is not None else AgentBank(self.N, P, dev)
-        self.P = self.bank.P
-        _seeded_draw(self.bank.buffer("u"), self.bank.buffer("target"), objective, seed, dev)
-        for name in ("u_out", "s", "s_out"):
-            self.bank.buffer(name, zero=True)
-        self.v = torch.ones(self.N, dtype=torch.float32, device=dev)
-        self.v_out = torch.ones(self.N, dtype=torch.float32, device=dev)
-        ops.separable_grad(self.bank.rows("u"), self.bank.rows("target"), self.bank.rows("s"), objective)
-        self.rounds = 0
 
     def round(self) -> None:
         """One push-sum gradient-tracking round (one call); swaps u / u_out, s / s_out and v / v_out."""
@@ -906,22 +902,8 @@ class SeparableGTPush:
         """The agents' estimates z = u / v (a read-out: torch's division)."""
         return self.bank.rows("u") / self.v[:, None]
 
-    def tracker(self) -> torch.Tensor:
-        return self.bank.rows("s")
-
     def weights(self) -> torch.Tensor:
         return self.v
-
-    def targets(self) -> torch.Tensor:
-        return self.bank.rows("target")
-
-    def consensus_error(self) -> float:
-        x = self.params()
-        return float((x - x.mean(0, keepdim=True)).norm() / max(1, x.shape[0]) ** 0.5)
-
-    def distance_to_optimum(self) -> float:
-        """_distance_to_mean_target of the estimates (agents along axis 0)."""
-        return _distance_to_mean_target(self.params(), self.targets(), 0, self.objective)
 
 
 class SeparableEXTRA:

@@ -15,9 +15,10 @@ matches the device's bit for bit).  A plain module (no fixtures): tests import
 it by name, tests/ being on sys.path.
 
 Below the restatement, what the gradient-tracking test files of the three
-layouts (parameter-major, agent-major ring, agent-major CSR) share: the device
-helpers of the GPU tiers (same_bits .. logistic_round) and the launch-free call
-builders of the host tiers (ENTRIES, recorder, host_args, host_call)."""
+layouts (parameter-major, agent-major ring, agent-major CSR, the last with its
+push-sum form) share: the device helpers and graphs of the GPU tiers (same_bits
+.. logistic_round) and the launch-free call builders of the host tiers
+(ENTRIES, recorder, host_args, host_call)."""
 import functools
 from fractions import Fraction
 
@@ -138,6 +139,30 @@ def regular(n):
     return G.random_regular_csr(n, 4, seed=n + 3), np.linspace(0.05, 0.45, n).astype(F32)
 
 
+@functools.lru_cache(maxsize=None)
+def irregular(n, values=True):
+    """A symmetric pattern with rows of degree 0, 1, 2, 3, 4, 5 and >= 9, the
+    degree-4 rows in the same 16-row blocks as the others: node 0 isolated; the
+    path 1 - 2 - ... - 6 with the chord 3 - 5; node 7 a hub joined to every
+    third node of the remainder (about 40 of them at most); the remainder 8 ..
+    n - 1 the circulant +-1, +-2 (4-regular).  Random positive values, or ones
+    (values=False: the pattern only)."""
+    from dolhip import graph as G
+    edges = {(i, i + 1) for i in range(1, 6)} | {(3, 5)}
+    m = n - 8
+    for i in range(m):
+        for k in (1, 2):
+            a, b = 8 + i, 8 + (i + k) % m
+            edges.add((min(a, b), max(a, b)))
+    for j in range(8, min(n, 8 + 120), 3):
+        edges.add((7, j))
+    A = np.zeros((n, n), F32)
+    rng = np.random.default_rng(n)
+    for a, b in edges:
+        A[a, b], A[b, a] = rng.random(2).astype(F32) + F32(0.05) if values else (1.0, 1.0)
+    return G.csr_from_dense(A).validate()
+
+
 def csr_dev(c, gpu):
     return tuple(torch.as_tensor(np.asarray(a, t), device=gpu) for a, t in
                  ((c.rowptr, np.int32), (c.col, np.int32), (c.val, np.float32)))
@@ -187,7 +212,7 @@ def logistic_round(mix, X, S, T, d, gpu, lr=0.1):
 
 
 # ---------------------------------------------------------------------------
-# shared by the host tiers: the three ops called without a launch
+# shared by the host tiers: the four ops called without a launch
 # ---------------------------------------------------------------------------
 # per op: the names of its four state matrices, the agent count of host_args,
 # its weight-vector arguments (positional ones first), the keywords its accepted call takes
@@ -196,6 +221,7 @@ ENTRIES = {
     "gt_ring": dict(state=("X", "S", "XO", "SO"), n=4, vectors=("w_prev", "w_next", "self_weight"),
                     kw=dict(P=10, n_rows=4)),
     "gt_csr": dict(state=("X", "S", "XO", "SO"), n=4, vectors=("self_weight",), kw=dict(P=10)),
+    "gt_push_csr": dict(state=("U", "S", "UO", "SO"), n=4, vectors=("v", "v_out", "self_weight"), kw=dict(P=10)),
 }
 
 
@@ -217,7 +243,9 @@ def host_args(op, dev, n=None, P=10, ld=12):
         ldn = (n + 3) // 4 * 4
         t = {k: mat(dev, P, n, ldn) for k in ("XT", "ST", "XO", "SO", "TT")}
     else:
-        t = {k: mat(dev, n, P, ld) for k in ("X", "S", "XO", "SO", "target")}
+        t = {k: mat(dev, n, P, ld) for k in ENTRIES[op]["state"] + ("target",)}
+    if op == "gt_push_csr":
+        t.update(v=vec(dev, n), v_out=vec(dev, n))
     if op == "gt_ring":
         t.update(w_prev=vec(dev, n), w_next=vec(dev, n))
     else:
@@ -229,5 +257,6 @@ def host_call(op, t, **kw):
     from dolhip import ops
     order = {"gt_csr_pm": ("XT", "ST", "XO", "SO", "rowptr", "col", "val", "TT"),
              "gt_ring": ("X", "S", "XO", "SO", "w_prev", "w_next", "target"),
-             "gt_csr": ("X", "S", "XO", "SO", "rowptr", "col", "val", "target")}[op]
+             "gt_csr": ("X", "S", "XO", "SO", "rowptr", "col", "val", "target"),
+             "gt_push_csr": ("U", "S", "UO", "SO", "rowptr", "col", "val", "target", "v", "v_out")}[op]
     return getattr(ops, op)(*(t[k] for k in order), **kw)

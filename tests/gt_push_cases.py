@@ -14,15 +14,14 @@ golden-pinned oracle calls and single numpy float32 operations:
 C = c + diag(d) is column-stochastic; row i of c lists i's in-neighbours.
 Matrices are agent-major [n, P], v is [n].  `grad` as in gt_cases.gt_round.
 Below it, the graphs the two tiers share: digraph(n), the reference ring's W as
-column-stochastic weights, and the irregular pattern of
-tests/test_gt_csr_gpu.py restated."""
+column-stochastic weights, and gt_cases.irregular under this module's name."""
 import functools
 
 import numpy as np
 
 import gt_cases
 import oracle
-from gt_cases import F32, ls_grad
+from gt_cases import F32, irregular, ls_grad  # noqa: F401  (irregular: used through this module too)
 
 
 def gt_push_round(U, S, T, v, c, d, lr, grad=ls_grad):
@@ -67,26 +66,3 @@ def reference_ring_weights(n):
     wt = gt_cases.ring(n)[0].transpose()
     c = G.CSR(wt.n_rows, wt.n_cols, wt.rowptr, wt.col, (wt.val * F32(0.5)).astype(F32)).validate()
     return c, np.full(n, 0.5, F32)
-
-
-@functools.lru_cache(maxsize=None)
-def irregular(n):
-    """tests/test_gt_csr_gpu.py's irregular(n) restated: rows of degree 0, 1, 2,
-    3, 4, 5 and >= 9, the degree-4 rows in the same 16-row blocks as the others
-    (node 0 isolated; the path 1 - ... - 6 with the chord 3 - 5; node 7 a hub
-    joined to every third node of the remainder; the remainder the circulant
-    +-1, +-2).  Random positive values."""
-    from dolhip import graph as G
-    edges = {(i, i + 1) for i in range(1, 6)} | {(3, 5)}
-    m = n - 8
-    for i in range(m):
-        for k in (1, 2):
-            a, b = 8 + i, 8 + (i + k) % m
-            edges.add((min(a, b), max(a, b)))
-    for j in range(8, min(n, 8 + 120), 3):
-        edges.add((7, j))
-    A = np.zeros((n, n), F32)
-    rng = np.random.default_rng(n)
-    for a, b in edges:
-        A[a, b], A[b, a] = rng.random(2).astype(F32) + F32(0.05)
-    return G.csr_from_dense(A).validate()

@@ -116,32 +116,10 @@ def test_beyond_the_parameter_major_cap(self_w, gpu):
 # ---------------------------------------------------------------------------
 # irregular degrees
 # ---------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def irregular(n):
-    """A symmetric pattern with rows of degree 0, 1, 2, 3, 4, 5 and >= 9, the
-    degree-4 rows in the same 16-row blocks as the others: node 0 isolated; the
-    path 1 - 2 - ... - 6 with the chord 3 - 5; node 7 a hub joined to every
-    third node of the remainder (about 40 of them at most); the remainder 8 ..
-    n - 1 the circulant +-1, +-2 (4-regular).  Random positive values."""
-    edges = {(i, i + 1) for i in range(1, 6)} | {(3, 5)}
-    m = n - 8
-    for i in range(m):
-        for k in (1, 2):
-            a, b = 8 + i, 8 + (i + k) % m
-            edges.add((min(a, b), max(a, b)))
-    for j in range(8, min(n, 8 + 120), 3):
-        edges.add((7, j))
-    A = np.zeros((n, n), F32)
-    rng = np.random.default_rng(n)
-    for a, b in edges:
-        A[a, b], A[b, a] = rng.random(2).astype(F32) + F32(0.05)
-    return G.csr_from_dense(A).validate()
-
-
 @pytest.mark.parametrize("n", [37, 520], ids=["n=37 small-n kernel", "n=520 pinned kernel"])
 @pytest.mark.parametrize("P", [1031, 7])
 def test_irregular_degrees(n, P, gpu):
-    c = irregular(n)
+    c = gt_cases.irregular(n)
     deg = np.diff(c.rowptr)
     assert {0, 1, 2, 3, 4, 5} <= set(deg.tolist()) and deg.max() >= 9
     assert 4 in deg[:16] and len(set(deg[:16].tolist())) >= 6 and (deg[n - 16:] == 4).any()

@@ -17,15 +17,20 @@ is launched.
   arithmetic: world 1 in-process, worlds 2 and 3 over gloo; the gathered
   parameters and trackers equal the unsharded host rounds bit for bit.
 * The launch geometry and indexing of csrc/gt_csr.hip restated in the manner
-  of tests/test_kernel_extents.py: gt_csr_xcd_kernel<32, 2, OBJ, SELF> (from 512
-  rows and 32 f4 columns: grid cdiv(nt, 8) * 8 * cdiv(n, 16), tile = (b >> 3) /
-  nrb * 8 + (b & 7); rows clamped to n - 1 for rowptr, the gathers, the centre
-  rows and the target row; stores r < n) and gt_csr_kernel<f4 / float, OBJ,
-  SELF> (the columns the pinned tiles leave over, small graphs, scalar columns:
-  16 rows per block, row group fastest).  Every buffer's touched range must lie
-  in [0, n * ld): on an exact-size mapped block an over-read faults.
-* The emitted code: 2 objectives x 2 self-weight forms of each kernel form,
-  none with a private segment (no scratch).
+  of tests/test_kernel_extents.py: gt_csr_xcd_kernel<R, 32, 2, OBJ, SELF> (from
+  512 rows and 32 f4 columns: grid cdiv(nt, 8) * 8 * cdiv(n, 16), tile = (b >>
+  3) / nrb * 8 + (b & 7); rows clamped to n - 1 for rowptr, the gathers, the
+  centre rows and the target row; stores r < n) and gt_csr_kernel<R, f4 /
+  float, OBJ, SELF> (the columns the pinned tiles leave over, small graphs,
+  scalar columns: 16 rows per block, row group fastest).  Both entry points
+  run these kernels (R = GtPlain for dol_gt_csr_f32, GtPushSum for
+  dol_gt_push_csr_f32); the push-sum round also reads v and v_out at the rows
+  of the self weights, after gt_push_v_kernel (one thread per row).  Every
+  buffer's touched range must lie in [0, n * ld), or [0, n) for a vector: on
+  an exact-size mapped block an over-read faults.
+* The emitted code: 2 rounds x 2 objectives x 2 self-weight forms of each
+  kernel form and the 2 forms of gt_push_v_kernel, none with a private segment
+  (no scratch).
 * tests/gt_cases.py::gt_round replayed on the 16-agent random 4-regular graph
   with Metropolis weights, least squares, lr 0.1, 200 rounds, P = 8: every
   agent within 1e-5 of the mean of the targets, where DGD with the same W and
@@ -56,9 +61,9 @@ from test_ops_args_gpu import mat, vec
 CPU = torch.device("cpu")
 F32 = np.float32
 I32 = torch.int32
-RPB = 16           # kGtCsrRows, and the rows of one block of the pinned kernel ((256 / XW) * XPASSES)
+RPB = 16           # kRows, and the rows of one block of the pinned kernel ((256 / XW) * XPASSES)
 XW, XPASSES = 32, 2  # the pinned tile: 32 f4 = 512 B of a row
-MIN_XCD_ROWS = 512   # kGtCsrMinXcdRows
+MIN_XCD_ROWS = 512   # kMinXcdRows
 
 
 # ---------------------------------------------------------------------------
@@ -324,12 +329,24 @@ def _block_neighbour_range(csr, n):
     return np.minimum.reduceat(lo, starts), np.maximum.reduceat(hi, starts)
 
 
-def gt_csr_extents(n, P, ld, csr, vec_ok=True):
-    """dol_gt_csr_f32 -> gt_csr_xcd_kernel<32, 2, *, *> over whole pinned tiles
-    (from 512 rows), gt_csr_kernel<f4, *, *> over the f4 columns left, then
-    gt_csr_kernel<float, *, *> over the scalar ones (all of them when !vec_ok)."""
+def gt_csr_extents(n, P, ld, csr, vec_ok=True, push=False):
+    """dol_gt_csr_f32 (push: dol_gt_push_csr_f32) -> gt_csr_xcd_kernel<R, 32, 2,
+    *, *> over whole pinned tiles (from 512 rows), gt_csr_kernel<R, f4, *, *>
+    over the f4 columns left, then gt_csr_kernel<R, float, *, *> over the scalar
+    ones (all of them when !vec_ok).  push: gt_push_v_kernel first, and the
+    main kernels read v and v_out at the rows where they read the self weights
+    W."""
     e = Ext()
     blk_lo, blk_hi = _block_neighbour_range(csr, n)
+    row_w = ("W", "v", "v_out") if push else ("W",)
+    if push:  # gt_push_v_kernel: one thread per row r < n, cdiv(n, 256) blocks
+        r = np.arange(cdiv(n, KT) * KT, dtype=np.int64)
+        r = r[r < n]
+        lo, hi = _row_neighbour_range(csr, n)
+        e.add("rowptr", r, r + 1)
+        e.add("v", np.minimum(lo[r], r), np.maximum(hi[r], r))  # v[col[e]] and v[r]
+        e.add("W", r, r)
+        e.add("v_out", r, r)
     n4, tail = (P // 4, P % 4) if vec_ok else (0, P)
     assert cdiv(n4, KT) * cdiv(n, RPB) <= 1 << 24 and cdiv(tail, KT) * cdiv(n, RPB) <= 1 << 24
     done4 = 0
@@ -353,7 +370,8 @@ def gt_csr_extents(n, P, ld, csr, vec_ok=True):
         e.add("rowptr", rc_lo, rc_hi + 1)
         for m in ("X", "S"):  # the gathers and the centre rows
             e.add(m, np.minimum(blk_lo[rb], rc_lo) * ld + c_lo, np.maximum(blk_hi[rb], rc_hi) * ld + c_hi)
-        e.add("W", rc_lo, rc_hi)
+        for m in row_w:
+            e.add(m, rc_lo, rc_hi)
         for m in ("T", "XO", "SO"):  # the target rows (clamped) and the stores (r < n): the same rows
             e.add(m, rc_lo * ld + c_lo, rc_hi * ld + c_hi)
         done4 = nt * XW
@@ -369,7 +387,8 @@ def gt_csr_extents(n, P, ld, csr, vec_ok=True):
         assert (c_first <= c_last).all()
         lo, hi = c_off + c_first * V, c_off + c_last * V + V - 1
         e.add("rowptr", r0, r1)
-        e.add("W", r0, r1 - 1)
+        for m in row_w:
+            e.add(m, r0, r1 - 1)
         for m in ("X", "S"):
             e.add(m, np.minimum(blk_lo[rg], r0) * ld + lo, np.maximum(blk_hi[rg], r1 - 1) * ld + hi)
         for m in ("T", "XO", "SO"):
@@ -378,14 +397,17 @@ def gt_csr_extents(n, P, ld, csr, vec_ok=True):
 
 
 def _sizes(n, ld):
-    return dict({m: n * ld for m in ("X", "S", "T", "XO", "SO")}, rowptr=n + 1, W=n)
+    return dict({m: n * ld for m in ("X", "S", "T", "XO", "SO")}, rowptr=n + 1, W=n, v=n, v_out=n)
 
 
-def _check_whole(e, n, P, ld):
+def _check_whole(e, n, P, ld, push=False):
     e.check(_sizes(n, ld))
     for m in ("T", "XO", "SO"):  # and nothing is left out
         assert e.r[m] == (0, (n - 1) * ld + P - 1), m
     assert e.r["rowptr"] == (0, n) and e.r["W"] == (0, n - 1)
+    assert ("v" in e.r, "v_out" in e.r) == (push, push)
+    if push:
+        assert e.r["v"] == (0, n - 1) and e.r["v_out"] == (0, n - 1)
 
 
 @pytest.mark.parametrize("n", [1024, 8192])
@@ -393,27 +415,14 @@ def test_extents_at_the_headline_shapes(n):
     """Exact-size mapped blocks: n * row_stride(P) floats per matrix."""
     P = 1 << 20
     ld = row_stride(P)
-    _check_whole(gt_csr_extents(n, P, ld, G.random_regular_csr(n, 4, seed=n + 3)), n, P, ld)
-
-
-def _irregular(n):
-    """test_gt_csr_gpu.py's irregular pattern: degrees 0, 1, 2, 3, 4, 5 and a hub."""
-    edges = {(i, i + 1) for i in range(1, 6)} | {(3, 5)}
-    m = n - 8
-    for i in range(m):
-        for k in (1, 2):
-            edges.add((min(8 + i, 8 + (i + k) % m), max(8 + i, 8 + (i + k) % m)))
-    for j in range(8, min(n, 8 + 120), 3):
-        edges.add((7, j))
-    A = np.zeros((n, n), F32)
-    for a, z in edges:
-        A[a, z] = A[z, a] = 1.0
-    return G.csr_from_dense(A)
+    csr = G.random_regular_csr(n, 4, seed=n + 3)
+    for push in (False, True):
+        _check_whole(gt_csr_extents(n, P, ld, csr, push=push), n, P, ld, push)
 
 
 @functools.lru_cache(maxsize=None)
 def _ragged_csr(n):
-    return _irregular(n) if n in (37, 520) else G.random_regular_csr(n, 4, seed=n + 3)
+    return gt_cases.irregular(n, values=False) if n in (37, 520) else G.random_regular_csr(n, 4, seed=n + 3)
 
 
 @pytest.mark.parametrize("P", [1, 7, 128, 131, 132, 300, 1031])
@@ -423,18 +432,21 @@ def test_extents_at_ragged_shapes(n, P):
     tests' ld = round_up(P, 4), and with every column scalar (odd ld, or an
     unaligned base)."""
     csr = _ragged_csr(n)
-    for ld, vec_ok in ((row_stride(P), True), ((P + 3) // 4 * 4, True), (P + 8 | 1, False), (P, False)):
-        _check_whole(gt_csr_extents(n, P, ld, csr, vec_ok), n, P, ld)
-    if P == 131 and n >= MIN_XCD_ROWS:  # one pinned tile, no left-over f4, a 3-float tail
-        e = gt_csr_extents(n, P, 132, csr)
-        assert e.r["X"][1] <= (n - 1) * 132 + 130
+    for push in (False, True):
+        for ld, vec_ok in ((row_stride(P), True), ((P + 3) // 4 * 4, True), (P + 8 | 1, False), (P, False)):
+            _check_whole(gt_csr_extents(n, P, ld, csr, vec_ok, push), n, P, ld, push)
+        if P == 131 and n >= MIN_XCD_ROWS:  # one pinned tile, no left-over f4, a 3-float tail
+            e = gt_csr_extents(n, P, 132, csr, push=push)
+            assert e.r["X"][1] <= (n - 1) * 132 + 130
 
 
 def test_extents_of_rows_past_element_2_pow_31():
     for n, ld in ((5, (1 << 29) + 64), (520, (1 << 22) + 64)):
-        e = gt_csr_extents(n, 1031, ld, G.random_regular_csr(n, 4, seed=n + 3))
-        e.check(_sizes(n, ld))
-        assert e.r["SO"][1] == (n - 1) * ld + 1030 >= 1 << 31
+        for push in (False, True):
+            e = gt_csr_extents(n, 1031, ld, G.random_regular_csr(n, 4, seed=n + 3), push=push)
+            e.check(_sizes(n, ld))
+            assert e.r["SO"][1] == (n - 1) * ld + 1030 >= 1 << 31
+            assert not push or e.r["v"] == e.r["v_out"] == (0, n - 1)
 
 
 # ---------------------------------------------------------------------------
@@ -460,16 +472,20 @@ def _private_segment_sizes(co):
 
 
 def test_gt_csr_kernels_are_counted_and_scratch_free(gt_csr_code_object):
-    """{least squares, logistic} x {no self weights, self weights} of each
-    kernel form: the pinned tiles, the 4 KiB f4 tiles, the scalar columns; no
-    private segment (nothing in scratch)."""
+    """{plain, push-sum} x {least squares, logistic} x {no self weights, self
+    weights} of each kernel form: the pinned tiles, the 4 KiB f4 tiles, the
+    scalar columns; gt_push_v_kernel with and without self weights; no private
+    segment (nothing in scratch)."""
     co = gt_csr_code_object
     xcd = _kernels(co, "gt_csr_xcd_kernel")
     small = _kernels(co, "gt_csr_kernel")
     f4, scalar = [k for k in small if "Dv4_f" in k], [k for k in small if "Dv4_f" not in k]
-    assert len(xcd) == 4 and len(f4) == 4 and len(scalar) == 4, (xcd, f4, scalar)
+    vk = _kernels(co, "gt_push_v_kernel")
+    assert len(xcd) == 8 and len(f4) == 8 and len(scalar) == 8 and len(vk) == 2, (xcd, f4, scalar, vk)
+    for form in (xcd, f4, scalar):  # 4 per round
+        assert sum("GtPlain" in k for k in form) == 4 and sum("GtPushSum" in k for k in form) == 4, form
     sizes = _private_segment_sizes(co)
-    for k in xcd + f4 + scalar:
+    for k in xcd + f4 + scalar + vk:
         assert sizes[k] == 0, f"{k}: a private segment of {sizes[k]} bytes (scratch)"
 
 

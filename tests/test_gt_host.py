@@ -1,9 +1,9 @@
 """Gradient tracking on the parameter-major bank, CPU tier (launch-free:
 ops._native.call is replaced by test_ops_args_gpu.Recorder where an op is
-called), and the rules the three ops share.
+called), and the rules the four ops share.
 
-* The rules that ops.gt_csr_pm, ops.gt_ring and ops.gt_csr state alike, each
-  tested once over the three (gt_cases.ENTRIES): an unknown objective, each
+* The rules that ops.gt_csr_pm, ops.gt_ring, ops.gt_csr and ops.gt_push_csr
+  state alike, each tested once over the four (gt_cases.ENTRIES): an unknown objective, each
   pair of the four state matrices aliased, bad weight vectors, CPU tensors.
   The rules of one layout are in tests/test_gt_ring_host.py and
   tests/test_gt_csr_host.py.

@@ -7,10 +7,10 @@ host restatement built from the golden-pinned oracle and single numpy float32
 operations (the two divisions among them: correctly rounded on both sides).
 Every bit test runs with an arbitrary positive v (linspace(0.5, 2, n)), CSR
 values that are not stochastic in any sense, and NaN in the inputs' padding
-columns.  The shapes play the roles they play in tests/test_gt_csr_gpu.py, the
-kernels having gt_csr.hip's geometry (16 rows per block; 512-B XCD-pinned tiles
-from 512 rows; 4 KiB tiles below that and for left-over columns; scalar columns
-for P % 4 and unaligned rows):
+columns.  The shapes play the roles they play in tests/test_gt_csr_gpu.py:
+both rounds run the kernels of csrc/gt_csr.hip (16 rows per block; 512-B
+XCD-pinned tiles from 512 rows; 4 KiB tiles below that and for left-over
+columns; scalar columns for P % 4 and unaligned rows):
   n  5 under a block, 17 ragged on the small-n kernel, 512 / 527 the pinned
      kernel, whole and ragged blocks;
   P  1 and 7 scalar tail only, 131 one pinned tile + a 3-float tail, 300 two

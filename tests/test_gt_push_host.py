@@ -7,11 +7,12 @@ MixingPlan.apply_gt_push, SeparableGTPush), CPU tier: nothing is launched.
   the library with addresses that are never dereferenced: null v / v_out, v and
   v_out aliased.
 * The rules of ops.gt_push_csr with ops._native.call replaced by
-  test_ops_args_gpu.Recorder: an unknown objective, aliased state matrices,
-  aliased v / v_out, a short or wrongly typed v or v_out.  A CPU matrix is
-  refused before the square-C rule is looked at (as for ops.gt_csr), so the
-  non-square C and the accepted call's argument tuple use device tensors: those
-  two tests carry the gpu marker, still with the Recorder and without a launch.
+  test_ops_args_gpu.Recorder: aliased state matrices, aliased v / v_out, a
+  short or wrongly typed v or v_out (an unknown objective and CPU tensors: with
+  the other ops in tests/test_gt_host.py).  A CPU matrix is refused before the
+  square-C rule is looked at (as for ops.gt_csr), so the non-square C and the
+  accepted call's argument tuple use device tensors: those two tests carry the
+  gpu marker, still with the Recorder and without a launch.
 * MixingPlan.apply_gt_push's routing by kind and SeparableGTPush's refusals.
 * CSR.transpose() and graph.push_sum_weights.
 * tests/gt_push_cases.py::gt_push_round replayed (least squares, P = 8, zero
@@ -109,12 +110,6 @@ def _call(t, **kw):
     return ops.gt_push_csr(*(t[k] for k in STATE + ("rowptr", "col", "val", "target", "v", "v_out")), **kw)
 
 
-def test_unknown_objective_is_refused(rec):
-    with pytest.raises(ValueError, match="gt_push_csr: objective must be one of"):
-        _call(_args(CPU), objective="hinge")
-    assert rec.calls == []
-
-
 @pytest.mark.parametrize("a,b", [(STATE[i], STATE[j]) for i in range(4) for j in range(i + 1, 4)])
 def test_two_state_matrices_the_same_tensor_are_refused(a, b, rec):
     t = _args(CPU)
@@ -151,12 +146,6 @@ def test_bad_weight_vectors_are_refused(name, bad, rec):
         t[name] = bad(4)
     with pytest.raises(ValueError, match=rf"{name}: expected contiguous float32 \[4\] on cpu"):
         _call(t, **kw)
-    assert rec.calls == []
-
-
-def test_cpu_tensors_are_refused(rec):
-    with pytest.raises(ops.DolNativeError, match="cpu"):
-        _call(_args(CPU), self_weight=vec(CPU, 4), objective="logistic", lr=0.5, P=10)
     assert rec.calls == []
 
 

@@ -6,8 +6,9 @@ tracing option in the same run; the program after `--`):
   python tools/gt_counters.py DIR --layout L --agents N [--params P] [--out profiles/gt_L_counters.json]
 Medians per launch, in KiB, per objective, of the layout's f4 kernel: L = ring
 gt_ring_dma_kernel (the objective is its second template argument), L = csr
-gt_csr_xcd_kernel (the pinned tiles: every f4 column at P = 2^20; its third),
-L = csr-push gt_push_csr_xcd_kernel (the same tiles; the program after `--` is
+gt_csr_xcd_kernel<GtPlain, ...> (the pinned tiles: every f4 column at P = 2^20;
+its fourth), L = csr-push gt_csr_xcd_kernel<GtPushSum, ...>, the same template's
+push-sum instantiations (the same tiles; the program after `--` is
 then `python tools/gt_push_ab.py --legs a ...`; the n-float v' kernel and the
 2 n floats of v the main kernel reads are not counted), L = extra-csr /
 extra-ring the EXTRA round's instantiations of the mixing kernels themselves,
@@ -26,8 +27,9 @@ import statistics
 
 
 # the measured kernel's demangled name up to its objective, the one group
-KERNELS = {"ring": r"gt_ring_dma_kernel<\d+, (\d+)", "csr": r"gt_csr_xcd_kernel<\d+, \d+, (\d+)",
-           "csr-push": r"gt_push_csr_xcd_kernel<\d+, \d+, (\d+)",
+KERNELS = {"ring": r"gt_ring_dma_kernel<\d+, (\d+)",
+           "csr": r"gt_csr_xcd_kernel<[^,<]*\bGtPlain, \d+, \d+, (\d+)",
+           "csr-push": r"gt_csr_xcd_kernel<[^,<]*\bGtPushSum, \d+, \d+, (\d+)",
            "extra-csr": r"csr_xcd_kernel<\d+, \d+, [^<]*ExtraEpi<(\d+)",
            "extra-ring": r"ring_mix_dma_kernel<\d+, [^<]*ExtraEpi<(\d+)"}
 
