@@ -295,7 +295,8 @@ __device__ __forceinline__ void gt_push_finish(f4 au, f4 as, f4 u, f4 s, f4 t, f
 
 // The EXTRA round (Shi, Ling, Wu, Yin, SIAM J. Optim. 25(2), 2015) on one
 // coordinate after its one mix ax = (W_off x), written once (ExtraEpi below, so
-// every agent-major mix kernel that takes an epilogue).  With W~ = (I + W) / 2
+// every agent-major mix kernel that takes an epilogue, and csr_pm_extra_kernel
+// on the parameter-major bank).  With W~ = (I + W) / 2
 // the method's two-step recursion is x' = W x - lr g(x) - c, c' = c + (x - W x) / 2,
 // c(0) = 0: the correction c is the agent's own row, so only x is mixed.  All
 // fp32, each operation rounded once, d the agent's self weight:
@@ -311,14 +312,16 @@ __device__ __forceinline__ void extra_finish(float ax, float x, float c, float t
   xo = __builtin_fmaf(neg_lr, separable_grad<OBJ>(x, t), ax) - c;
   co = __builtin_fmaf(0.5f, r, c);
 }
-// the same on four coordinates of one agent
-template <int OBJ>
-__device__ __forceinline__ void extra_finish(f4 ax, f4 x, f4 c, f4 t, float d, bool self, float neg_lr, f4& xo,
+// the same on four coordinates; d: one agent's weight (agent-major) or four agents' (parameter-major)
+template <int OBJ, class D>
+__device__ __forceinline__ void extra_finish(f4 ax, f4 x, f4 c, f4 t, D d, bool self, float neg_lr, f4& xo,
                                              f4& co) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    float xe, ce;
-    extra_finish<OBJ>(ax[j], x[j], c[j], t[j], d, self, neg_lr, xe, ce);
+    float dj, xe, ce;
+    if constexpr (std::is_same_v<D, f4>) dj = d[j];
+    else dj = d;
+    extra_finish<OBJ>(ax[j], x[j], c[j], t[j], dj, self, neg_lr, xe, ce);
     xo[j] = xe;
     co[j] = ce;
   }

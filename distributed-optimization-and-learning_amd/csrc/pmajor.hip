@@ -77,6 +77,37 @@
 // (profiles/gt_pm_counters.json): FETCH_SIZE 6 291 733 KiB (x 2: 1.00004 x the
 // 3 N P 4 read), WRITE_SIZE 8 389 153 KiB (1.00006 x the 2 N P 4 written).
 //
+// csr_pm_extra_kernel: config 3's EXTRA round (x' = W x - lr g(x) - c, c' = c +
+// (x - W x) / 2, extra_finish of dol_launch.h) in the same pipeline.  Only X is
+// gathered, so a stage is the DGD round's mode-2 stage with the correction in
+// the momentum's place: X, T and C images; the own x, t, c are f4 LDS reads;
+// X' goes to YT and c' back to C in place, after the barrier that retires the
+// stage's DMA (a C p-row belongs to one workgroup): 5 N P 4 bytes per round.
+// csr_pm_gt_kernel's packed stage issue; 81 (least squares) / 87 (logistic)
+// VGPRs, no scratch (hipcc's resource remarks; 85 / 91 at 80 KiB x 2, 81 / 87 at
+// 64 KiB x 2, no scratch either).  Geometry, rr4 + Metropolis self weights, a
+// build that took the geometry per call, one process, same buffers, medians of
+// 5 alternating windows, least squares / logistic ms at 1024 x 2^20 (4096 x
+// 2^18), window spread 0.1-0.6 %, profiles/extra_pm_geom.jsonl:
+//   80 KiB x 2  4.33 / 4.35 (3.42 / 3.67)
+//   64 KiB x 2  4.22 / 4.23 (3.41 / 3.51)
+//   48 KiB x 3  4.09 / 4.15 (3.45 / 3.56)     <- both objectives
+// 48 KiB x 3 beats 80 KiB x 2 by 5.4 / 4.7 % at 1024 agents and by 3.1 % for
+// logistic at 4096; at 4096 agents (one p-row per stage in every geometry)
+// least squares is 0.7 % behind 80 KiB x 2 and logistic 1.2 % behind 64 KiB x 2.
+// Legs (tools/extra_ab.py --layout pm, profiles/extra_pm_ab.jsonl; another box,
+// one process, same buffers, medians of 5 windows): (a) this kernel, (b)
+// csr_pm_gt_kernel, (c) the least-squares / logistic + momentum DGD round (the
+// same five streams), (d) ops.extra_csr on the same problem agent-major (equal
+// bit for bit); HBM = 5 N P 4 bytes over (a) at 8 TB/s:
+//   1024 x 2^20  least squares (a) 3.86 (b) 3.95 (c) 3.90 (d) 4.98 ms, (a)/(c) 0.990, (a)/(d) 0.775, HBM 70 %
+//                logistic      (a) 3.87 (b) 4.36 (c) 3.84 (d) 4.97,    1.007, 0.779, 69 %
+//   4096 x 2^18  least squares (a) 4.14 (b) 3.60 (c) 4.02 (d) 4.89,    1.031, 0.847, 65 %
+//                logistic      (a) 4.12 (b) 4.39 (c) 4.01 (d) 4.91,    1.029, 0.839, 65 %
+// Counters per launch at 1024 x 2^20 (profiles/extra_pm_counters.json):
+// FETCH_SIZE x 2 1.00004 x the 3 N P 4 read, WRITE_SIZE 1.0004 x / 1.00009 x the
+// 2 N P 4 written.
+//
 // Tried and retired (each was a launch variant behind an environment switch;
 // the code last existed in commit 2d96633):
 //  * DOL_PM_DGD_GEOM, the fused round's stage geometry forced to 64 KiB x 2,
@@ -643,6 +674,167 @@ __global__ __launch_bounds__(T) void csr_pm_gt_kernel(const float* __restrict__ 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ----------------------------------------------------------------------------
+// The EXTRA round of config 3 in one pass (extra_finish, dol_launch.h):
+//   x_i' = sum_j W_ij x_j - lr grad f_i(x_i) - c_i
+//   c_i' = c_i + (x_i - sum_j W_ij x_j) / 2
+// with W = W_off (CSR) + diag(self_w).  Not in the reference (as the
+// gradient-tracking round above); the mix is its consensus
+// (DIST/clients.py:61-69).  Only X is gathered: a stage is the DGD round's
+// mode-2 stage with the correction where the momentum is -- sr p-rows of X
+// images (xw floats each), then of T images, then of C images (nw floats each)
+// -- brought in by one LDS-DMA ring.  The centre x is an f4 LDS read of the X
+// image, t and c of theirs.  X' goes to YT and c' back to C in place: a C
+// p-row is read (by DMA) and written by the one workgroup that owns its stage,
+// and the write is issued after the barrier that retires the stage's DMA, as
+// the momentum's is in csr_pm_kernel.  X, T, C in, X', C' out: 5 x 4 bytes per
+// coordinate.
+// ----------------------------------------------------------------------------
+struct PmExtra {
+  float* YT; int64_t ldy;
+  const float* T; int64_t ldt;
+  float* C; int64_t ldc;
+  const float* D;  // self weights [n_rows] or NULL
+  float neg_lr;
+};
+
+// One stage of the round: the X images at im0, the T images behind them, the
+// C images behind those; two buffer stores per (p-row, quad), dead lanes
+// pointed out of range as in mix_stage.
+template <int T, int OBJ>
+__device__ __forceinline__ void extra_stage(const Quad (&Q)[1], f4 dw, const float* __restrict__ im0, const PmExtra& e,
+                                            int n_rows, int64_t P, int64_t p0, int xw, int nw, int sr, int spt, int q0,
+                                            int g, int GR, const int32_t* __restrict__ rowptr,
+                                            const int32_t* __restrict__ col, const float* __restrict__ val) {
+  const int nq = (n_rows + 3) / 4;
+  const int64_t rows_here = std::min<int64_t>(sr, P - p0);
+  const rsrc_t ry = make_rsrc(e.YT + p0 * e.ldy, static_cast<uint32_t>(rows_here * e.ldy * 4));
+  const rsrc_t rc = make_rsrc(e.C + p0 * e.ldc, static_cast<uint32_t>(rows_here * e.ldc * 4));
+  const float* tim0 = im0 + sr * xw;
+  const float* cim0 = tim0 + sr * nw;
+  const bool self = e.D != nullptr;
+  const int q = q0;
+  const int qc = q < nq ? q : 0;
+  for (int u = 0; u < spt; ++u) {
+    const int pr = g + u * GR;
+    const bool prow_ok = pr < rows_here;
+    const int prc = pr < sr ? pr : 0;
+    const float* xim = im0 + prc * xw;
+    const f4 ax = mix_quad(Q[0], xim, q, rowptr, col, val);
+    const f4 xv = *reinterpret_cast<const f4*>(xim + 4 * qc);
+    const f4 tv = *reinterpret_cast<const f4*>(tim0 + prc * nw + 4 * qc);
+    const f4 cv = *reinterpret_cast<const f4*>(cim0 + prc * nw + 4 * qc);
+    f4 xo, co;
+    extra_finish<OBJ>(ax, xv, cv, tv, dw, self, e.neg_lr, xo, co);
+    const uint32_t offy = static_cast<uint32_t>((pr * e.ldy + 4 * q) * 4);
+    const uint32_t offc = static_cast<uint32_t>((pr * e.ldc + 4 * q) * 4);
+    if (4 * q + 3 < n_rows || q >= nq) {  // whole quad, or none (dropped)
+      const bool ok = prow_ok && q < nq;
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, xo), ry, ok ? offy : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, co), rc, ok ? offc : kOOB, 0, kNT);
+    } else {  // the ragged last quad (elements named one by one: hipcc 7.2 stored
+              // element 0 four times from a loop over y[a] here)
+      const int left = n_rows - 4 * q;  // 1..3
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.x), ry, prow_ok ? offy : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.y), ry, prow_ok && left > 1 ? offy + 4 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xo.z), ry, prow_ok && left > 2 ? offy + 8 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(co.x), rc, prow_ok ? offc : kOOB, 0, kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(co.y), rc, prow_ok && left > 1 ? offc + 4 : kOOB, 0,
+                                            kNT);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(co.z), rc, prow_ok && left > 2 ? offc + 8 : kOOB, 0,
+                                            kNT);
+    }
+  }
+}
+
+// T threads per workgroup, SF floats per stage buffer, NBUF buffers; one quad
+// per thread (at most 4 T agents).  The ring, the counted wait, the stage order
+// and the packed stage issue are csr_pm_gt_kernel's; kStores = 2.
+template <int T, int SF, int NBUF, int OBJ>
+__global__ __launch_bounds__(T) void csr_pm_extra_kernel(const float* __restrict__ XT, int64_t ldx, int n_rows,
+                                                         int64_t P, int xw, int sr, int qp_log2, int spt,
+                                                         int64_t n_stages, int nseg,
+                                                         const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const float* __restrict__ val, PmExtra e, int nw) {
+  constexpr int kDma = SF / 4 / T;
+  static_assert(kDma * 4 * T == SF, "a stage is a whole number of DMA rounds");
+  extern __shared__ __attribute__((aligned(16))) float img[];  // NBUF x SF
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q0 = tid & ((1 << qp_log2) - 1);
+  const int g = tid >> qp_log2;
+  const int GR = T >> qp_log2;
+  const int nnz = rowptr[n_rows];
+  Quad Q[1];
+  if (nnz > 0) load_quad(Q[0], q0, n_rows, nnz, rowptr, col, val);
+  else Q[0] = Quad{};
+  const f4 dw = load_self_weights(e.D, q0, n_rows);
+
+  const int64_t W = gridDim.x / nseg, seg = blockIdx.x % nseg, wl = blockIdx.x / nseg;
+  const int64_t seg_len = (n_stages + nseg - 1) / nseg;
+  const int64_t seg_n = std::max<int64_t>(0, std::min<int64_t>(seg_len, n_stages - seg * seg_len));
+  const int64_t nk = wl < seg_n ? (seg_n - wl + W - 1) / W : 0;
+  auto stage_of = [&](int64_t k) { return seg * seg_len + wl + k * W; };
+  // This thread's kDma pieces of a stage, classified once as in
+  // csr_pm_gt_kernel: piece d is 16 B of operand sel (0 X, 1 T, 2 C; 3 dead) in
+  // p-row pr of the stage, poff floats from that operand's row p0.
+  const int xq = xw / 4, nq4 = nw / 4, nr4 = (n_rows + 3) / 4;
+  const int nX = sr * xq, nTM = sr * nq4;
+  int poff[kDma], pmeta[kDma];
+#pragma unroll
+  for (int d = 0; d < kDma; ++d) {
+    const int pc = d * T + tid;
+    int sel = 3, pr = 0, off = 0;
+    if (pc < nX) {
+      pr = pc / xq;
+      const int j4 = pc - pr * xq;
+      if (j4 < nr4) {
+        sel = 0;
+        off = static_cast<int>(pr * ldx) + 4 * j4;
+      }
+    } else if (pc - nX < 2 * nTM) {
+      const int pt = pc - nX, h = pt >= nTM ? 1 : 0, r = pt - h * nTM;
+      pr = r / nq4;
+      sel = 1 + h;
+      off = static_cast<int>(pr * (h ? e.ldc : e.ldt)) + 4 * (r - pr * nq4);
+    }
+    poff[d] = off;
+    pmeta[d] = pr | sel << 16;
+  }
+  auto issue = [&](int64_t k) {  // stage k of this workgroup -> buffer k % NBUF; dead pieces re-read XT[0..3]
+    float* dst = img + (k % NBUF) * SF;
+    const int64_t p0 = stage_of(k) * sr;
+    const float* bx = XT + p0 * ldx;
+    const float* bt = e.T + p0 * e.ldt;
+    const float* bc = e.C + p0 * e.ldc;
+#pragma unroll
+    for (int d = 0; d < kDma; ++d) {
+      const int sel = pmeta[d] >> 16, pr = pmeta[d] & 0xffff;
+      const float* base = sel == 0 ? bx : sel == 1 ? bt : bc;
+      const float* src = sel != 3 && p0 + pr < P ? base + poff[d] : XT;
+      __builtin_amdgcn_global_load_lds(DOL_GPTR(src), DOL_LPTR(dst + (d * T + wave * 64) * 4), 16, 0, kNT);
+    }
+  };
+  constexpr int kStores = 2;  // buffer stores per (p-row, quad): X' and C'
+#pragma unroll
+  for (int k = 0; k < NBUF - 1; ++k)
+    if (k < nk) issue(k);
+  for (int64_t k = 0; k < nk; ++k) {
+    const int64_t ahead = std::min<int64_t>(nk - 1, k + NBUF - 2) - k;
+    wait_vmcnt(static_cast<int>(std::min<int64_t>(63, kStores * spt * std::min<int64_t>(k, NBUF - 1) + kDma * ahead)));
+    __builtin_amdgcn_s_barrier();  // every wave's share landed (the C images too: their p-rows may be written now);
+                                   // buffer (k-1) % NBUF is free
+    if (k + NBUF - 1 < nk) issue(k + NBUF - 1);
+    extra_stage<T, OBJ>(Q, dw, img + (k % NBUF) * SF, e, n_rows, P, stage_of(k) * sr, xw, nw, sr, spt, q0, g, GR,
+                        rowptr, col, val);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this stage's LDS reads are done before the next barrier
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
 // G = g(X, T) elementwise over rows x cols (V = f4 columns or the scalar tail
 // from c_off), row loads and stores nontemporal; either bank layout.
 template <typename V, int OBJ>
@@ -887,6 +1079,64 @@ int gt_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, const float* ST
   return check_launch(nm);
 }
 
+// The EXTRA round: validation in gt_csr_pm_impl's order and wording, then
+// csr_pm_extra_kernel in the small geometry (1024-thread workgroups, one per
+// CU, one quad per thread).
+int extra_csr_pm_impl(const char* nm, const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                      const int32_t* rowptr, const int32_t* col, const float* val, const float* self_w,
+                      const float* TT, int64_t ldt, float* CT, int64_t ldc, int32_t objective, float lr,
+                      int32_t nseg_req, hipStream_t s) {
+  if (objective != 0 && objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 or 1", nm);
+  if (nseg_req < 0 || nseg_req > 256) return fail(DOL_EINVAL, "%s: stage order %d outside [0, 256]", nm, nseg_req);
+  if (n < 0 || P < 0) return fail(DOL_EINVAL, "%s: negative size", nm);
+  if (n == 0 || P == 0) { dol::g_err[0] = '\0'; return DOL_OK; }
+  if (!XT || !YT || !TT || !CT || !rowptr || !col || !val) return fail(DOL_EINVAL, "%s: null pointer", nm);
+  if (n > kGtMaxAgents)
+    return fail(DOL_EINVAL, "%s: the EXTRA round takes at most %d agents (got %d)", nm, kGtMaxAgents, n);
+  const int nq = (n + 3) / 4;
+  const int nw = 4 * nq;
+  for (const int64_t ld : {ldx, ldy, ldt, ldc})
+    if (ld % 4 || ld < nw)
+      return fail(DOL_EINVAL, "%s: leading dimensions must be multiples of 4 covering the rounded-up agent count", nm);
+  if ((reinterpret_cast<uintptr_t>(XT) | reinterpret_cast<uintptr_t>(YT) | reinterpret_cast<uintptr_t>(TT) |
+       reinterpret_cast<uintptr_t>(CT)) & 15u)
+    return fail(DOL_EINVAL, "%s: XT, YT, TT and CT must be 16-B aligned", nm);
+  if (XT == YT) return fail(DOL_EINVAL, "%s: XT and YT alias (Jacobi mix needs two buffers)", nm);
+  if (CT == XT || CT == YT || CT == TT)
+    return fail(DOL_EINVAL, "%s: CT aliases XT, YT or TT (the correction is updated in place)", nm);
+  // geometry: X + T + C p-rows per stage, xw + 2 nw floats each (48 KiB at
+  // 4096 agents, so every agent count fits): 48 KiB x 3 for both objectives,
+  // the ring that won at 1024 x 2^20 (the file's header)
+  const int xw = (n + 255) / 256 * 256;
+  constexpr int SF = 12288, NB = 3;  // the kernel's SF and NBUF (LDS size)
+  int sr = SF / (xw + 2 * nw);
+  int qp_log2 = 0;
+  while ((1 << qp_log2) < nq) ++qp_log2;
+  const int gr = kT1 >> qp_log2;
+  if (sr >= gr) sr = std::min(sr / gr * gr, 4 * gr);
+  const int spt = (sr + gr - 1) / gr;
+  if (sr < 1) return fail(DOL_EINVAL, "%s: a p-row of X, T and C exceeds a stage", nm);
+  // a stage's offsets are 32-bit: the stores' buffer offsets and the DMA pieces' float offsets
+  if (int64_t(sr) * std::max({ldx, ldy, ldt, ldc}) * 4 >= (int64_t(1) << 31))
+    return fail(DOL_EINVAL, "%s: leading dimension too large", nm);
+  const int64_t n_stages = (P + sr - 1) / sr;
+  const int ncu = n_cus();
+  if (ncu <= 0) return fail(DOL_EINVAL, "%s: no device", nm);
+  const int64_t grid = std::min<int64_t>(ncu, n_stages);
+  const int proc = g_pm_nseg.load(std::memory_order_relaxed);
+  int nseg = nseg_req > 0 ? nseg_req : proc > 0 ? proc : env_int("DOL_PM_NSEG", 8);
+  if (nseg < 1 || grid % nseg) nseg = 1;
+  const PmExtra e{YT, ldy, TT, ldt, CT, ldc, self_w, -lr};
+  auto go = [&](auto kern) {
+    const int lds = NB * SF * 4;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kT1), lds, s, XT, ldx, n, P, xw, sr, qp_log2, spt,
+                       n_stages, nseg, rowptr, col, val, e, nw);
+  };
+  dispatch([&](auto oc) { go(csr_pm_extra_kernel<kT1, SF, NB, decltype(oc)::value>); }, Ints<0, 1>{objective});
+  return check_launch(nm);
+}
+
 }  // namespace
 
 extern "C" {
@@ -906,6 +1156,23 @@ int dol_gt_csr_pm_ex_f32(const float* XT, int64_t ldx, const float* ST, int64_t 
   DOL_DIMS_OK("dol_gt_csr_pm_f32", ldx, lds, ldxo, ldso, ldt, P);
   return gt_csr_pm_impl("dol_gt_csr_pm_f32", XT, ldx, ST, lds, XO, ldxo, SO, ldso, n, P, rowptr, col, val, self_w, TT,
                         ldt, objective, lr, nseg, s);
+}
+
+int dol_extra_csr_pm_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                         const int32_t* rowptr, const int32_t* col, const float* val, const float* self_w,
+                         const float* TT, int64_t ldt, float* CT, int64_t ldc, int32_t objective, float lr,
+                         hipStream_t s) {
+  return dol_extra_csr_pm_ex_f32(XT, ldx, YT, ldy, n, P, rowptr, col, val, self_w, TT, ldt, CT, ldc, objective, lr, 0,
+                                 s);
+}
+
+int dol_extra_csr_pm_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                            const int32_t* rowptr, const int32_t* col, const float* val, const float* self_w,
+                            const float* TT, int64_t ldt, float* CT, int64_t ldc, int32_t objective, float lr,
+                            int32_t nseg, hipStream_t s) {
+  DOL_DIMS_OK("dol_extra_csr_pm_f32", ldx, ldy, ldt, ldc, P);
+  return extra_csr_pm_impl("dol_extra_csr_pm_f32", XT, ldx, YT, ldy, n, P, rowptr, col, val, self_w, TT, ldt, CT, ldc,
+                           objective, lr, nseg, s);
 }
 
 int dol_separable_grad_f32(const float* X, int64_t ldx, const float* T, int64_t ldt, float* G, int64_t ldg,

@@ -14,6 +14,7 @@ Layers:
             bank, any sparse W, ops.gt_csr), SeparableGTPM, and SeparableGTPush
             (push-sum, column-stochastic weights, ops.gt_push_csr); EXTRA, which
             mixes the parameters only: SeparableEXTRA (ops.extra_csr / ops.extra_ring)
+            and SeparableEXTRAPM (parameter-major bank, ops.extra_csr_pm)
 The reference-shaped APIs live beside this package:
   weighted_average/  (Simulator, DecFedAvg, FedLCon, Client, ...)
   primal_dual/       (Server, FedAvg_/FedProx_/FedAdmm_Server/_Client)

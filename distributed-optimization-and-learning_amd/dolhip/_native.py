@@ -103,6 +103,10 @@ SIGNATURES = {
                            _i32, _f32, _ptr],
     "dol_extra_ring_edges_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr,
                                  _i64, _i32, _f32, _ptr],
+    "dol_extra_csr_pm_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i32,
+                             _f32, _ptr],
+    "dol_extra_csr_pm_ex_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i32,
+                                _f32, _i32, _ptr],
     "dol_separable_grad_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i32, _ptr],
     "dol_transpose_f32": [_ptr, _i64, _ptr, _i64, _i64, _i64, _ptr],
     "dol_csr_slab_nk": [_i32],

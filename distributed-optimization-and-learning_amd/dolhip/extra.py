@@ -2,8 +2,10 @@
 3: one round in one HBM pass on the agent-major bank with any sparse W
 (dol_extra_csr_f32), on the agent-major ring (dol_extra_ring_f32, wrap-around
 or the blocks of a sharded ring through its halo form) and on a ring block's
-two boundary rows (dol_extra_ring_edges_f32).  ops re-exports the calls as
-ops.extra_csr / ops.extra_ring / ops.extra_ring_edges.
+two boundary rows (dol_extra_ring_edges_f32), and on the parameter-major bank
+with any sparse W up to ops.PM_DGD_MAX_AGENTS agents (dol_extra_csr_pm_f32).
+ops re-exports the calls as ops.extra_csr / ops.extra_ring /
+ops.extra_ring_edges / ops.extra_csr_pm.
 
 With W~ = (I + W) / 2 the paper's recursion
   x(k+2) = (I + W) x(k+1) - W~ x(k) - lr [grad f(x(k+1)) - grad f(x(k))],   x(1) = W x(0) - lr grad f(x(0))
@@ -25,9 +27,10 @@ gradient-tracking rounds take: symmetric, doubly stochastic, positive diagonal
 off-diagonal part plus `self_weight`.
 
 The argument rules are the validators of ops.py and gt.py (_ring_args,
-_csr_args, _check_halos, _leading_dims, _check_objective, pm_steps' square-W
-check) plus one stated here: corr is none of X, Y, target.
-tests/test_extra_host.py pins them without a launch.
+_csr_args, _pm_args, _check_halos, _leading_dims, _check_objective, pm_steps'
+square-W check) plus one stated here: corr is none of X, Y, target.
+tests/test_extra_host.py and tests/test_extra_pm_host.py pin them without a
+launch.
 """
 from __future__ import annotations
 
@@ -87,6 +90,35 @@ def extra_csr(X: torch.Tensor, Y: torch.Tensor, rowptr: torch.Tensor, col: torch
                  _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val), _ops._ptr(self_weight), target.data_ptr(),
                  ldt, corr.data_ptr(), ldc, obj, float(lr), _ops._stream(X))
     return Y
+
+
+def extra_csr_pm(XT: torch.Tensor, YT: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor,
+                 TT: torch.Tensor, corr: torch.Tensor, self_weight: Optional[torch.Tensor] = None,
+                 objective: str = "least_squares", lr: float = 0.01, P: Optional[int] = None,
+                 nseg: Optional[int] = None) -> torch.Tensor:
+    """extra_csr's round on the parameter-major bank (dol_extra_csr_pm_f32):
+    XT the parameters, TT the targets, corr the corrections (zero before the
+    first round), all [P, >= n] like mix_csr_pm's XT (n = rowptr length - 1);
+    YT receives x', corr is updated in place.  ax is mix_csr_pm's sum and the
+    rest as extra_csr: the bits of extra_csr on the transposed matrices.  The
+    rules of this op are extra_csr's, on mix_csr_pm's layout, and at most
+    ops.PM_DGD_MAX_AGENTS agents.  nseg as mix_csr_pm (None: the order tuned
+    for the XT / YT pair on the plain mix, which only writes YT).  Returns YT."""
+    obj = _extra_rules("extra_csr_pm", XT, YT, TT, corr, objective)
+    n = rowptr.shape[0] - 1
+    if n > _ops.PM_DGD_MAX_AGENTS:
+        raise ValueError(f"extra_csr_pm: the EXTRA round takes at most {_ops.PM_DGD_MAX_AGENTS} agents (got {n})")
+    P, n, _, ldx, ldy = _ops._pm_args(XT, YT, rowptr, col, val, n, P)
+    _, ldc, ldt = _leading_dims((("XT", XT), ("corr", corr)), ("TT", TT), P, n, pmajor=True)
+    if self_weight is not None:
+        _ops._check_array("self_weight", self_weight, torch.float32, n, XT.device)
+    _check_square(rowptr, col, n)
+    if nseg is None:
+        nseg = _ops._pm_auto(_ops._pm_mix(XT, YT, rowptr, col, val, ldx, ldy, n, n, P), XT, YT, ldx, ldy, n, n, P)
+    _native.call("dol_extra_csr_pm_ex_f32", XT.data_ptr(), ldx, YT.data_ptr(), ldy, n, P, rowptr.data_ptr(),
+                 _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val), _ops._ptr(self_weight), TT.data_ptr(), ldt,
+                 corr.data_ptr(), ldc, obj, float(lr), int(nseg), _ops._stream(XT))
+    return YT
 
 
 def extra_ring(X: torch.Tensor, Y: torch.Tensor, w_prev: torch.Tensor, w_next: torch.Tensor, target: torch.Tensor,

@@ -1091,7 +1091,7 @@ from .gt import gt_csr, gt_csr_pm, gt_push_csr, gt_ring, separable_grad  # noqa:
 
 # ---------------------------------------------------------------------------
 # EXTRA, the exact round that mixes the parameters only, on the agent-major
-# bank and ring (extra.py, on the validators above and gt.py's):
-# extra_csr, extra_ring, extra_ring_edges.
+# bank and ring and on the parameter-major bank (extra.py, on the validators
+# above and gt.py's): extra_csr, extra_ring, extra_ring_edges, extra_csr_pm.
 # ---------------------------------------------------------------------------
-from .extra import extra_csr, extra_ring, extra_ring_edges  # noqa: E402,F401
+from .extra import extra_csr, extra_csr_pm, extra_ring, extra_ring_edges  # noqa: E402,F401

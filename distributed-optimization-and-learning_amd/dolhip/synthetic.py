@@ -975,6 +975,75 @@ class SeparableEXTRA:
         return _distance_to_mean_target(self.params(), self.targets(), 0, self.objective)
 
 
+class SeparableEXTRAPM:
+    """Config 3 with EXTRA on the parameter-major bank, SeparableGTPM's sibling
+    and SeparableEXTRA's round on that layout: one kernel and one pass over X,
+    the corrections and the targets (dol_extra_csr_pm_f32), the five streams of
+    SeparableDGDPM's round with momentum, for any sparse W.  Not a reference
+    algorithm.  The weights W = plan's CSR + diag(self_weight) and the step
+    size are SeparableEXTRA's: see its docstring.
+
+    XT / YT (parameters in and out), TT and CT (the corrections, zero at the
+    start, updated in place) are [P, ld], ld = round_up(N, 4), like
+    SeparableGTPM's matrices, with the same seeded init.  Dense plans and more
+    than ops.PM_DGD_MAX_AGENTS agents are refused."""
+
+    def __init__(self, plan: MixingPlan, P: int, objective: str = "least_squares", lr: float = 0.01,
+                 self_weight=None, seed: int = 2028, _state=None):
+        from . import ops
+        if plan.n_rows > ops.PM_DGD_MAX_AGENTS:
+            raise ValueError(f"the EXTRA round on the parameter-major bank takes at most {ops.PM_DGD_MAX_AGENTS} agents")
+        if plan.kind == "dense":
+            raise ValueError("the EXTRA round mixes a sparse (CSR) W")
+        self.plan, self.P, self.objective, self.lr = plan, int(P), objective, float(lr)
+        self.N = plan.n_rows
+        self.ld = (self.N + 3) // 4 * 4
+        dev = plan.device
+        self.self_weight = _gt_rules(objective, self_weight, self.N, dev)
+        self.XT = torch.zeros((self.P, self.ld), dtype=torch.float32, device=dev)
+        self.YT, self.TT, self.CT = (torch.zeros_like(self.XT) for _ in range(3))
+        if _state is None:
+            _seeded_draw(self.XT[:, :self.N], self.TT[:, :self.N], objective, seed, dev)
+        self.rounds = 0
+
+    @classmethod
+    def from_agent_major(cls, prob: "SeparableEXTRA") -> "SeparableEXTRAPM":
+        """The problem of a SeparableEXTRA on this bank: its plan, self weights
+        and lr, and its current parameters, targets and corrections transposed
+        (the two layouts draw their seeded init in different element orders)."""
+        from . import ops
+        self = cls(prob.plan, prob.P, prob.objective, prob.lr, self_weight=prob.self_weight, _state=True)
+        for src, dst in ((prob.params(), self.XT), (prob.targets(), self.TT), (prob.correction(), self.CT)):
+            ops.transpose(src, dst, prob.N, prob.P)
+        self.rounds = prob.rounds
+        return self
+
+    def round(self) -> None:
+        """One EXTRA round (one kernel); CT is updated in place; swaps XT / YT."""
+        from . import ops
+        p = self.plan
+        ops.extra_csr_pm(self.XT, self.YT, p.rowptr, p.col, p.val, self.TT, self.CT, self_weight=self.self_weight,
+                         objective=self.objective, lr=self.lr, P=self.P)
+        self.XT, self.YT = self.YT, self.XT
+        self.rounds += 1
+
+    def params(self) -> torch.Tensor:
+        """Agent-major copy [N, P] of the current parameters (diagnostic)."""
+        return self.XT[:, :self.N].T.contiguous()
+
+    def correction(self) -> torch.Tensor:
+        """Agent-major copy [N, P] of the corrections c_i (diagnostic)."""
+        return self.CT[:, :self.N].T.contiguous()
+
+    def consensus_error(self) -> float:
+        x = self.XT[:, :self.N]
+        return float((x - x.mean(1, keepdim=True)).norm() / max(1, self.N) ** 0.5)
+
+    def distance_to_optimum(self) -> float:
+        """_distance_to_mean_target of the parameters (agents along axis 1)."""
+        return _distance_to_mean_target(self.XT[:, :self.N], self.TT[:, :self.N], 1, self.objective)
+
+
 class TimeVaryingMLPGossip:
     """BASELINE config 5 as a first-class round: N agents, each an
     nn.Sequential(Linear(d, h), ReLU(), Linear(h, c)) row of the bank, a new

@@ -541,6 +541,35 @@ int dol_extra_ring_edges_f32(const float* X, int64_t ldx, float* Y, int64_t ldy,
                              const float* halo_prev, const float* halo_next, const float* w_prev,
                              const float* w_next, const float* w_self /* nullable */, const float* target,
                              int64_t ldt, float* corr, int64_t ldc, int32_t objective, float lr, hipStream_t s);
+/*
+ * dol_extra_csr_f32's round (Shi, Ling, Wu, Yin 2015; not in the reference, in
+ * place of DIST/simulators.py:147-162 with the consensus of DIST/clients.py:61-69)
+ * on the parameter-major bank in one pass, in dol_mix_csr_pm_f32's layout and
+ * rounding: XT, YT (= x'), TT (the targets) and CT (the corrections) are
+ * [P][ld] like XT there; W = W_off + diag(self_w), W_off the square CSR (0 <=
+ * col < n).  For every coordinate p and agent i:
+ *   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e)
+ *   self_w != NULL:  ax = fl(ax + fl(self_w[i] * x_i))
+ *   r  = fl(x_i - ax);  x' = fl(fma(-lr, g(x_i, t_i), ax) - c_i);  c' = fma(0.5, r, c_i)   written over c_i
+ * the bits of dol_extra_csr_f32 on the transposed matrices.  Start with CT = 0.
+ * The round streams X, T, C in and X', C' out once (dol_dgd_csr_pm_f32's five
+ * streams with momentum); a p-row of CT is read and written by one workgroup.
+ * Limits: n <= 4096; every leading dimension a multiple of 4 >= round_up(n, 4);
+ * the four matrices 16-B aligned; YT distinct from XT (a Jacobi mix); CT
+ * distinct from XT, YT and TT (it is updated in place); no null pointers but
+ * self_w; objective 0 or 1.  n < 0 or P < 0: DOL_EINVAL.  n == 0 or P == 0:
+ * DOL_OK, nothing launched.  Stream-ordered; allocates nothing; does not
+ * synchronise.
+ */
+int dol_extra_csr_pm_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                         const int32_t* rowptr, const int32_t* col, const float* val,
+                         const float* self_w /* nullable */, const float* TT, int64_t ldt, float* CT, int64_t ldc,
+                         int32_t objective, float lr, hipStream_t s);
+/* dol_extra_csr_pm_f32 with the stage order per call (see dol_mix_csr_pm_ex_f32). */
+int dol_extra_csr_pm_ex_f32(const float* XT, int64_t ldx, float* YT, int64_t ldy, int32_t n, int64_t P,
+                            const int32_t* rowptr, const int32_t* col, const float* val,
+                            const float* self_w /* nullable */, const float* TT, int64_t ldt, float* CT, int64_t ldc,
+                            int32_t objective, float lr, int32_t nseg, hipStream_t s);
 
 /*
  * G[r][c] = g(X[r][c], T[r][c]) for r < rows, c < cols: the gradient of the

@@ -21,6 +21,20 @@ The correction is updated in place, so it keeps growing over a leg's calls (X
 is not swapped): the values stay finite and far from denormal, which is all a
 timing needs.  `frac` = 5 N P 4 bytes over a leg's median as a share of 8 TB/s.
   python tools/extra_ab.py --agents 1024 [--params 1048576] [--pad 0] [--legs abcdefg] [--objectives least_squares,logistic] [--reps 5] [--inner 10] [--note TEXT] [--out profiles/extra_ab.jsonl]
+
+--layout pm: the round on the parameter-major bank (ops.extra_csr_pm), the same
+graph and weights, matrices [params, round_up(agents, 4)], the stage order left
+to the ops (tuned for the XT / YT pair on first use, as a caller gets it)
+(profiles/extra_pm_ab.jsonl; the recorded runs: 1024 x 2^20 and 4096 x 2^18):
+  (a) one ops.extra_csr_pm call;
+  (b) one ops.gt_csr_pm call on the same graph (X and S gathered);
+  (c) one ops.dgd_csr_pm call with momentum 0.5: the same five streams (corr's
+      buffer as the momentum) through the pipeline (a) is built on;
+  (d) one ops.extra_csr call on the same problem agent-major (transposed copies
+      of X and T, a Y and a corr of their own).  Its first call from a zero
+      correction is compared with (a)'s (`bits_equal_agent_major`: all of X'
+      and corr).
+  python tools/extra_ab.py --layout pm --agents 1024 [--params 1048576] [--legs abcd] [--objectives least_squares,logistic] [--reps 5] [--inner 10] [--note TEXT] [--out profiles/extra_pm_ab.jsonl]
 """
 import argparse
 import json
@@ -38,18 +52,100 @@ from dolhip import ops  # noqa: E402
 from dolhip.synthetic import ring_gt_weights  # noqa: E402
 from gt_ab import PEAK, csr_dev, median, ring_csr, same_bits, timed  # noqa: E402
 
+PM_NAMES = {"a": "extra_csr_pm", "b": "gt_csr_pm", "c": "dgd_csr_pm_momentum", "d": "extra_csr"}
 NAMES = {"a": "extra_csr", "b": "gt_csr", "c": "dgd_csr_momentum", "d": "composed", "e": "extra_ring", "f": "gt_ring",
          "g": "dgd_ring_momentum"}
 
 
+def pm_main(a):
+    dev = torch.device("cuda")
+    n, P, lr = a.agents, a.params, a.lr
+    ld = (n + 3) // 4 * 4
+    w_off, d = G.metropolis_weights(G.random_regular_csr(n, 4, seed=a.seed))
+    rp, col, val = csr_dev(w_off, dev)
+    ws = torch.as_tensor(d, device=dev)
+
+    def matrix():
+        return torch.zeros(P, ld, device=dev)[:, :n]
+    g = torch.Generator(device=dev).manual_seed(9)
+    XT, TT, YT, CT = (matrix() for _ in range(4))
+    XT.normal_(generator=g)
+    TT.normal_(generator=g)
+    if "b" in a.legs:
+        ST, SO = matrix(), matrix()
+    if "d" in a.legs:  # the same problem agent-major
+        X, T, Y, C = (torch.zeros(n, P, device=dev) for _ in range(4))
+    out = open(a.out, "a") if a.out else None
+
+    for objective in a.objectives.split(","):
+        if objective == "logistic":  # targets +-feature, in p-row blocks: no bank-sized temporaries
+            for r in range(0, P, 1 << 16):
+                blk = TT[r:r + (1 << 16)]
+                blk.mul_(torch.where(torch.rand(blk.shape, generator=g, device=dev) < 0.5, -1.0, 1.0))
+        kw = dict(objective=objective, lr=lr)
+        legs = {
+            "a": lambda: ops.extra_csr_pm(XT, YT, rp, col, val, TT, CT, self_weight=ws, **kw),
+            "b": lambda: ops.gt_csr_pm(XT, ST, YT, SO, rp, col, val, TT, self_weight=ws, **kw),
+            "c": lambda: ops.dgd_csr_pm(XT, YT, rp, col, val, TT, CT, steps=1, momentum=0.5, **kw),
+            "d": lambda: ops.extra_csr(X, Y, rp, col, val, T, C, self_weight=ws, **kw),
+        }
+        legs = {k: f for k, f in legs.items() if k in a.legs}
+        same = None
+        if "d" in legs:
+            ops.transpose(XT, X, P, n)
+            ops.transpose(TT, T, P, n)
+        if "a" in legs and "d" in legs:
+            C.zero_()
+            legs["d"]()
+            ops.transpose(Y, YT, n, P)  # YT as the transposes' landing place: (a) overwrites it below
+            want_x = YT.clone()
+            ops.transpose(C, YT, n, P)
+            want_c = YT.clone()
+            CT.zero_()
+            legs["a"]()
+            same = same_bits(YT, want_x) and same_bits(CT, want_c)
+            del want_x, want_c
+        t = {k: [] for k in legs}
+        for k, f in legs.items():  # each leg from its own start state: zero corr / momentum, s = g(x, t)
+            CT.zero_()
+            if k == "d":
+                C.zero_()
+            if k == "b":
+                ops.separable_grad(XT, TT, ST, objective)
+            for _ in range(a.warmup):  # clocks up, code objects loaded, the stage order tuned
+                f()
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            for k, f in legs.items():
+                t[k].append(timed(f, a.inner))
+        m = {k: median(x) for k, x in t.items()}
+        r = {"layout": "pm", "agents": n, "params": P, "ld": ld,
+             "graph": f"random 4-regular, seed {a.seed}, Metropolis weights", "objective": objective, "lr": lr,
+             "bits_equal_agent_major": same, "note": a.note}
+        for k in legs:
+            r[PM_NAMES[k] + "_ms"], r[PM_NAMES[k] + "_all"] = m[k], t[k]
+            r[PM_NAMES[k] + "_frac"] = 5 * n * P * 4 / (m[k] / 1e3) / PEAK
+        for num, den in (("a", "b"), ("a", "c"), ("a", "d")):
+            if num in m and den in m:
+                r[f"{num}_over_{den}"] = m[num] / m[den]
+                r[f"{num}_over_{den}_pairs"] = [x / y for x, y in zip(t[num], t[den])]
+        line = json.dumps(r)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layout", default="am", choices=("am", "pm"), help="am: the agent-major legs; pm: the "
+                    "parameter-major ones")
     ap.add_argument("--agents", type=int, default=1024)
     ap.add_argument("--params", type=int, default=1 << 20)
     ap.add_argument("--pad", type=int, default=0, help="ld = params + pad")
     ap.add_argument("--seed", type=int, default=2028, help="of the random 4-regular graph")
     ap.add_argument("--lr", type=float, default=0.1)
-    ap.add_argument("--legs", default="abcdefg")
+    ap.add_argument("--legs", default=None, help="default: abcdefg (am), abcd (pm)")
     ap.add_argument("--objectives", default="least_squares,logistic")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--inner", type=int, default=10, help="calls per timed window")
@@ -57,6 +153,10 @@ def main():
     ap.add_argument("--note", default=None, help="free text kept in every row (e.g. the build measured)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     a = ap.parse_args()
+    if a.legs is None:
+        a.legs = "abcd" if a.layout == "pm" else "abcdefg"
+    if a.layout == "pm":
+        return pm_main(a)
     dev = torch.device("cuda")
     n, P, lr, ld = a.agents, a.params, a.lr, a.params + a.pad
     w_off, d = G.metropolis_weights(G.random_regular_csr(n, 4, seed=a.seed))

@@ -14,7 +14,9 @@ then `python tools/gt_push_ab.py --legs a ...`; the n-float v' kernel and the
 extra-ring the EXTRA round's instantiations of the mixing kernels themselves,
 csr_xcd_kernel<32, 2, ExtraEpi<OBJ, SELF>> and ring_mix_dma_kernel<4,
 ExtraEpi<OBJ, SELF>, ...> (the program after `--` is then `python
-tools/extra_ab.py --legs a ...` or `--legs e ...`; the same five streams),
+tools/extra_ab.py --legs a ...` or `--legs e ...`; the same five streams), L =
+extra-pm csr_pm_extra_kernel on the parameter-major bank (the objective is its
+fourth template argument; `python tools/extra_ab.py --layout pm --legs a ...`),
 against the algorithmic 3 N P 4 read and 2 N P 4 written.  FETCH_SIZE counts
 half the bytes of a wide streaming read on gfx950, so `read_over_algorithmic`
 doubles it."""
@@ -31,7 +33,8 @@ KERNELS = {"ring": r"gt_ring_dma_kernel<\d+, (\d+)",
            "csr": r"gt_csr_xcd_kernel<[^,<]*\bGtPlain, \d+, \d+, (\d+)",
            "csr-push": r"gt_csr_xcd_kernel<[^,<]*\bGtPushSum, \d+, \d+, (\d+)",
            "extra-csr": r"csr_xcd_kernel<\d+, \d+, [^<]*ExtraEpi<(\d+)",
-           "extra-ring": r"ring_mix_dma_kernel<\d+, [^<]*ExtraEpi<(\d+)"}
+           "extra-ring": r"ring_mix_dma_kernel<\d+, [^<]*ExtraEpi<(\d+)",
+           "extra-pm": r"csr_pm_extra_kernel<\d+, \d+, \d+, (\d+)"}
 
 
 def main():
