@@ -1,7 +1,8 @@
 // gt_ring.hip — one gradient-tracking round (DIGing / NEXT) on the agent-major
 // ring in one HBM pass: dol_gt_ring_f32, the ring sibling of dol_gt_csr_pm_f32
-// (pmajor.hip).  Its own translation unit, so ring.o and its pinned kernels
-// stay as they are.
+// (pmajor.hip), and dol_gt_ring_edges_f32, the two boundary rows of a sharded
+// block.  Its own translation unit, so ring.o and its pinned kernels stay as
+// they are.
 //
 // Layout as ring.hip: agent k's vector is row k of a row-major fp32 matrix.
 // Two row matrices, the parameters X and the trackers S, go through ONE ring
@@ -183,6 +184,47 @@ __global__ __launch_bounds__(kThreads) void gt_ring_kernel(GtRing a, const float
   }
 }
 
+// ----------------------------------------------------------------------------
+// The two boundary rows of a sharded ring block in ONE launch (the multi-GPU
+// round, dolhip.parallel_gt.sharded_ring_gt_step: the interior rows run while
+// the halo rows of X and S travel, then these two), the sibling of
+// ring_edges_kernel: blockIdx.y = 0 -> row 0 (previous rows = the two prev
+// halos), 1 -> row n_rows - 1 (next rows = the two next halos); with
+// n_rows == 1 only y = 0 runs and uses all four halos, with n_rows == 2 each
+// edge row's inner neighbour is the other edge row.  V = f4 over the 16-B
+// columns, float from c_off on for the scalar ones.  The lane is gt_ring_lane,
+// so the bits are dol_gt_ring_f32's.  Plain loads and stores: two rows of a
+// block, nothing to keep out of L2.
+// ----------------------------------------------------------------------------
+template <typename V, int OBJ, bool SELF>
+__global__ __launch_bounds__(kThreads) void gt_ring_edges_kernel(GtRing a, const float* __restrict__ wprev,
+                                                                 const float* __restrict__ wnext,
+                                                                 const float* __restrict__ wself, int n_rows,
+                                                                 int64_t c_off, int64_t ncols_v) {
+  const int64_t c = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (c >= ncols_v) return;
+  const int r = blockIdx.y == 0 ? 0 : n_rows - 1;
+  auto at = [&](const float* row) { return reinterpret_cast<const V*>(row + c_off)[c]; };
+  const V xp = at(a.xrow(r - 1, n_rows)), x = at(a.xrow(r, n_rows)), xn = at(a.xrow(r + 1, n_rows));
+  const V sp = at(a.srow(r - 1, n_rows)), s = at(a.srow(r, n_rows)), sn = at(a.srow(r + 1, n_rows));
+  const V t = at(a.T + int64_t(r) * a.ldt);
+  const float wp = wprev[r], wn = wnext[r], ws = SELF ? wself[r] : 0.0f;
+  V xo, so;
+  if constexpr (Vec<V>::W == 1) {
+    gt_ring_lane<OBJ, SELF>(xp, x, xn, sp, s, sn, t, wp, wn, ws, a.neg_lr, xo, so);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float xe, se;
+      gt_ring_lane<OBJ, SELF>(xp[j], x[j], xn[j], sp[j], s[j], sn[j], t[j], wp, wn, ws, a.neg_lr, xe, se);
+      xo[j] = xe;
+      so[j] = se;
+    }
+  }
+  reinterpret_cast<V*>(a.XO + int64_t(r) * a.ldxo + c_off)[c] = xo;
+  reinterpret_cast<V*>(a.SO + int64_t(r) * a.ldso + c_off)[c] = so;
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,6 +267,37 @@ int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, fl
     if (cs.tail > 0)
       hipLaunchKernelGGL((gt_ring_kernel<OBJ, SELF>), dim3(static_cast<unsigned>(nctt * cdiv(n_rows, kGtTailRows))),
                          dim3(kThreads), 0, s, a, w_prev, w_next, w_self, n_rows, cs.n4 * 4, cs.tail, nctt);
+  }, Ints<0, 1>{objective}, Bool{w_self != nullptr});
+  return check_launch(nm);
+}
+
+int dol_gt_ring_edges_f32(const float* X, int64_t ldx, const float* S, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                          int64_t ldso, int32_t n_rows, int64_t P, const float* x_halo_prev,
+                          const float* x_halo_next, const float* s_halo_prev, const float* s_halo_next,
+                          const float* w_prev, const float* w_next, const float* w_self, const float* target,
+                          int64_t ldt, int32_t objective, float lr, hipStream_t s) {
+  const char* nm = "dol_gt_ring_edges_f32";
+  const GtRows m{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt};
+  DOL_CHECKED(m.check(nm, n_rows, P, !w_prev || !w_next || !x_halo_prev || !x_halo_next || !s_halo_prev ||
+                                         !s_halo_next));
+  if (const int rc = GtRows::objective_ok(nm, objective)) return rc;
+  const bool vec_ok = m.vec_ok() && aligned16(x_halo_prev) && aligned16(x_halo_next) && aligned16(s_halo_prev) &&
+                      aligned16(s_halo_next);
+  const ColSplit cs = split_cols(P, vec_ok);
+  const int64_t nct4 = cdiv(cs.n4, kThreads), nctt = cdiv(cs.tail, kThreads);
+  if (nct4 > kMaxBlocks || nctt > kMaxBlocks) return fail(DOL_EINVAL, "%s: problem too large for one launch", nm);
+  const unsigned ny = n_rows == 1 ? 1u : 2u;
+  const GtRing a{X, ldx, S, lds, XO, ldxo, SO, ldso, target, ldt, x_halo_prev, x_halo_next, s_halo_prev, s_halo_next,
+                 -lr};
+  dispatch([&](auto obj, auto self) {
+    constexpr int OBJ = decltype(obj)::value;
+    constexpr bool SELF = decltype(self)::value;
+    if (cs.n4 > 0)
+      hipLaunchKernelGGL((gt_ring_edges_kernel<f4, OBJ, SELF>), dim3(static_cast<unsigned>(nct4), ny), dim3(kThreads),
+                         0, s, a, w_prev, w_next, w_self, n_rows, int64_t(0), cs.n4);
+    if (cs.tail > 0)
+      hipLaunchKernelGGL((gt_ring_edges_kernel<float, OBJ, SELF>), dim3(static_cast<unsigned>(nctt), ny),
+                         dim3(kThreads), 0, s, a, w_prev, w_next, w_self, n_rows, cs.n4 * 4, cs.tail);
   }, Ints<0, 1>{objective}, Bool{w_self != nullptr});
   return check_launch(nm);
 }

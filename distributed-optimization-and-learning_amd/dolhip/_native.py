@@ -93,6 +93,8 @@ SIGNATURES = {
                              _i64, _i32, _f32, _i32, _ptr],
     "dol_gt_ring_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                         _ptr, _ptr, _i64, _i32, _f32, _ptr],
+    "dol_gt_ring_edges_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                              _ptr, _ptr, _ptr, _i64, _i32, _f32, _ptr],
     "dol_gt_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64,
                        _i32, _f32, _ptr],
     "dol_gt_push_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,

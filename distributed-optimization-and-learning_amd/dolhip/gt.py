@@ -1,8 +1,9 @@
 """Gradient tracking (DIGing / NEXT) for BASELINE config 3: one round in one
 HBM pass on the parameter-major bank (dol_gt_csr_pm_f32, any sparse W, at most
 ops.GT_MAX_AGENTS agents), on the agent-major ring (dol_gt_ring_f32, any
-number of agents, and the blocks of a sharded ring through its halo form) and
-on the agent-major bank with any sparse W (dol_gt_csr_f32, any number of
+number of agents, and the blocks of a sharded ring through its halo form, with
+dol_gt_ring_edges_f32 for a block's two boundary rows: ops.gt_ring_edges,
+rules pinned by tests/test_gt_sharded_host.py) and on the agent-major bank with any sparse W (dol_gt_csr_f32, any number of
 agents, and the column blocks of a column-sharded bank), and the device
 gradient of the separable losses (dol_separable_grad_f32) that starts the
 trackers.  ops re-exports the calls as ops.gt_csr_pm / ops.gt_ring /
@@ -136,6 +137,35 @@ def gt_ring(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor
     _native.call("dol_gt_ring_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(), ldso, n,
                  P, hp[0], hp[1], hp[2], hp[3], w_prev.data_ptr(), w_next.data_ptr(), _ops._ptr(self_weight),
                  target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
+    return XO, SO
+
+
+def gt_ring_edges(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, w_prev: torch.Tensor,
+                  w_next: torch.Tensor, target: torch.Tensor, halos, self_weight: Optional[torch.Tensor] = None,
+                  objective: str = "least_squares", lr: float = 0.01, P: Optional[int] = None,
+                  n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rows 0 and n_rows - 1 of gt_ring's halo form in one launch
+    (dol_gt_ring_edges_f32): the second half of a sharded ring's round, once
+    the halo rows have arrived.  Arguments as gt_ring, the matrices and weight
+    vectors the whole block's; halos: (x_prev, x_next, s_prev, s_next), all
+    four required.  Only rows 0 and n_rows - 1 of XO / SO are written, with
+    the bits gt_ring writes there.  Returns (XO, SO)."""
+    obj = _check_objective("gt_ring_edges", objective)
+    P = X.shape[1] if P is None else P
+    n = X.shape[0] if n_rows is None else n_rows
+    state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
+    _distinct_state("gt_ring_edges", state)
+    for nm, w in (("w_prev", w_prev), ("w_next", w_next)) + ((("self_weight", self_weight),) if self_weight is not None
+                                                              else ()):
+        _ops._check_array(nm, w, torch.float32, n, X.device)
+    if halos is None or len(halos) != 4 or any(h is None for h in halos):
+        raise ValueError("gt_ring_edges needs all four halos")
+    ldx, ld_s, ldxo, ldso, ldt = _leading_dims(state, ("target", target), P, n)
+    for nm, h in zip(("x_prev", "x_next", "s_prev", "s_next"), halos):
+        _ops._check_vec(f"halos {nm}", h, P, X.device)
+    _native.call("dol_gt_ring_edges_f32", X.data_ptr(), ldx, S.data_ptr(), ld_s, XO.data_ptr(), ldxo, SO.data_ptr(),
+                 ldso, n, P, *(h.data_ptr() for h in halos), w_prev.data_ptr(), w_next.data_ptr(),
+                 _ops._ptr(self_weight), target.data_ptr(), ldt, obj, float(lr), _ops._stream(X))
     return XO, SO
 
 

@@ -1084,10 +1084,11 @@ from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noq
 # Gradient tracking on the parameter-major bank, on the agent-major ring and
 # on the agent-major bank with any sparse W (gt.py, which builds on the
 # validators above and on pm_steps' square-W check): gt_csr_pm, gt_ring,
-# gt_csr, separable_grad; and gt_csr's push-sum form for column-stochastic
-# weights, gt_push_csr.
+# gt_ring_edges (a sharded ring block's two boundary rows), gt_csr,
+# separable_grad; and gt_csr's push-sum form for column-stochastic weights,
+# gt_push_csr.
 # ---------------------------------------------------------------------------
-from .gt import gt_csr, gt_csr_pm, gt_push_csr, gt_ring, separable_grad  # noqa: E402,F401
+from .gt import gt_csr, gt_csr_pm, gt_push_csr, gt_ring, gt_ring_edges, separable_grad  # noqa: E402,F401
 
 # ---------------------------------------------------------------------------
 # EXTRA, the exact round that mixes the parameters only, on the agent-major

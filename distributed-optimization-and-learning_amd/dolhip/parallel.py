@@ -36,7 +36,7 @@ import torch.distributed as dist
 from . import ops
 from .bank import device_matrix, row_stride
 from .parallel_extra import column_sharded_extra_step, sharded_ring_extra_step
-from .parallel_gt import column_sharded_gt_step
+from .parallel_gt import column_sharded_gt_step, sharded_ring_gt_step
 
 # Fail fast instead of hanging: every collective of the engine's
 # process groups is bounded by this timeout.  The reference has no collectives
@@ -248,6 +248,10 @@ class ShardedRing:
     # extra_step(target, corr, self_w=None, **kw): one EXTRA round on the local block with
     # dgd_step's halo schedule (only x has halos); corr in place; swaps x / y (parallel_extra.py)
     extra_step = sharded_ring_extra_step
+
+    # gt_step(s, s_out, target, self_w=None, **kw): one gradient-tracking round on the local block; the
+    # boundary rows of x and s travel in one message per direction; swaps x / y and returns (s_out, s) (parallel_gt.py)
+    gt_step = sharded_ring_gt_step
 
 
 def column_bounds(P: int, world: int, rank: int, align: int = 64) -> Tuple[int, int]:

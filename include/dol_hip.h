@@ -411,6 +411,25 @@ int dol_gt_ring_f32(const float* X, int64_t ldx, const float* S, int64_t lds, fl
                     const float* s_halo_prev, const float* s_halo_next, const float* w_prev, const float* w_next,
                     const float* w_self /* nullable */, const float* target, int64_t ldt, int32_t objective,
                     float lr, hipStream_t s);
+/*
+ * Rows 0 and n_rows - 1 of dol_gt_ring_f32 with halos, in one launch (see
+ * dol_mix_ring_edges_f32; not in the reference, in place of
+ * DIST/simulators.py:147-162 / DIST/clients.py:61-69): the second half of a
+ * sharded ring's gradient-tracking round, once the halo rows of X and S have
+ * arrived.  All four halos are required (there is no wrap-around form); X, S,
+ * w_prev, w_next, w_self and target are the whole block's (n_rows rows /
+ * [n_rows]), of which rows 0, 1, n_rows - 2 and n_rows - 1 of X and S and rows
+ * 0 and n_rows - 1 of the others are read; nothing but rows 0 and n_rows - 1
+ * of XO and SO, columns [0, P), is written.  n_rows == 1: the one row mixes
+ * from all four halos; n_rows == 2: each row's inner neighbour is the other
+ * row.  The bits of dol_gt_ring_f32 on the same block.  Other argument rules
+ * as dol_gt_ring_f32.
+ */
+int dol_gt_ring_edges_f32(const float* X, int64_t ldx, const float* S, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                          int64_t ldso, int32_t n_rows, int64_t P, const float* x_halo_prev,
+                          const float* x_halo_next, const float* s_halo_prev, const float* s_halo_next,
+                          const float* w_prev, const float* w_next, const float* w_self /* nullable */,
+                          const float* target, int64_t ldt, int32_t objective, float lr, hipStream_t s);
 
 /*
  * One gradient-tracking round (DIGing / NEXT) of BASELINE config 3 on the
