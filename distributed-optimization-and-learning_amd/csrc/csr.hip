@@ -1,5 +1,6 @@
 // csr.hip — the generic sparse (CSR) mix on the agent-major bank and its
-// fused DGD and EXTRA rounds: 4 KiB column tiles, or XCD-pinned 512 B tiles from 512 rows.
+// fused DGD and EXTRA rounds (EXTRA also with the gradient fed as a row matrix):
+// 4 KiB column tiles, or XCD-pinned 512 B tiles from 512 rows.
 //
 // Dropped launch variant (8192 x 2^20; the default's bits; code last present at 1a824fc):
 //   DOL_CSR_PASSES=1|4: csr_xcd_kernel with 8 / 32 rows per block instead of 16: 512-B tiles 17.94 ms
@@ -225,6 +226,19 @@ int dol_extra_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_
   const char* nm = "dol_extra_csr_f32";
   const ExtraArgs e{target, ldt, corr, ldc, self_w, objective, lr};
   return with_extra_epi<false>(nm, e, X, ldx, Y, n <= 0 || P <= 0, P, [&](auto epi, bool evec) {
+    return mix_csr_impl(nm, X, ldx, n, Y, ldy, n, P, rowptr, col, val, epi, evec, s);
+  });
+}
+
+// the same round with the gradient fed as the row matrix G where the target is read (ExtraEpi<kObjGradRow>);
+// its gradient-tracking sibling dol_gt_grad_csr_f32 has kernels of its own (grad_rounds.hip)
+int dol_extra_grad_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n, int64_t P,
+                           const int32_t* rowptr, const int32_t* col, const float* val, const float* self_w,
+                           const float* G, int64_t ldg, float* corr, int64_t ldc, float lr, hipStream_t s) {
+  DOL_DIMS_OK("dol_extra_grad_csr_f32", ldx, ldy, P, ldg, ldc);
+  const char* nm = "dol_extra_grad_csr_f32";
+  const ExtraArgs e{G, ldg, corr, ldc, self_w, kObjGradRow, lr};
+  return with_extra_grad_epi<false>(nm, e, X, ldx, Y, n <= 0 || P <= 0, P, [&](auto epi, bool evec) {
     return mix_csr_impl(nm, X, ldx, n, Y, ldy, n, P, rowptr, col, val, epi, evec, s);
   });
 }

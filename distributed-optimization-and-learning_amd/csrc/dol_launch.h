@@ -293,6 +293,38 @@ __device__ __forceinline__ void gt_push_finish(f4 au, f4 as, f4 u, f4 s, f4 t, f
   }
 }
 
+// The gradient-FED gradient-tracking round on one coordinate after its two
+// mixes (gt_grad_csr_*_kernel, grad_rounds.hip): DIGing with the tracker update
+// at the front of the round, s_k = W s_{k-1} + G_k - G_{k-1}, then x_{k+1} = W
+// x_k - lr s_k, the gradients g (this round's) and gp (last round's) read from
+// rows that something else computed.  All fp32, each operation rounded once, d
+// the agent's self weight:
+//   self:  ax = fl(ax + fl(d x));  as = fl(as + fl(d s))
+//   s' = fl(fl(as + g) - gp)
+//   x' = fma(-lr, s', ax)
+// x' takes the agent's own new tracker, so the round is one pass; from s = 0 and
+// gp = 0 the first round gives s' = g.  Without self weights x and s are not read.
+__device__ __forceinline__ void gt_grad_finish(float ax, float as, float x, float s, float g, float gp, float d,
+                                               bool self, float neg_lr, float& xo, float& so) {
+  if (self) {
+    ax = ax + d * x;
+    as = as + d * s;
+  }
+  so = (as + g) - gp;
+  xo = __builtin_fmaf(neg_lr, so, ax);
+}
+// the same on four coordinates of one agent
+__device__ __forceinline__ void gt_grad_finish(f4 ax, f4 as, f4 x, f4 s, f4 g, f4 gp, float d, bool self, float neg_lr,
+                                               f4& xo, f4& so) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float xe, se;
+    gt_grad_finish(ax[j], as[j], x[j], s[j], g[j], gp[j], d, self, neg_lr, xe, se);
+    xo[j] = xe;
+    so[j] = se;
+  }
+}
+
 // The EXTRA round (Shi, Ling, Wu, Yin, SIAM J. Optim. 25(2), 2015) on one
 // coordinate after its one mix ax = (W_off x), written once (ExtraEpi below, so
 // every agent-major mix kernel that takes an epilogue, and csr_pm_extra_kernel
@@ -304,12 +336,19 @@ __device__ __forceinline__ void gt_push_finish(f4 au, f4 as, f4 u, f4 s, f4 t, f
 //   r  = fl(x - ax)
 //   x' = fl(fma(-lr, g(x, t), ax) - c)                       g = separable_grad<OBJ>
 //   c' = fma(0.5, r, c)
+// OBJ == kObjGradRow is the gradient-FED round (dol_extra_grad_csr_f32 only):
+// the row loaded in the target's place IS the gradient, g = t, and
+// separable_grad is not called.
+constexpr int kObjGradRow = 2;
 template <int OBJ>
 __device__ __forceinline__ void extra_finish(float ax, float x, float c, float t, float d, bool self, float neg_lr,
                                              float& xo, float& co) {
   if (self) ax = ax + d * x;
   const float r = x - ax;
-  xo = __builtin_fmaf(neg_lr, separable_grad<OBJ>(x, t), ax) - c;
+  float g;
+  if constexpr (OBJ == kObjGradRow) g = t;
+  else g = separable_grad<OBJ>(x, t);
+  xo = __builtin_fmaf(neg_lr, g, ax) - c;
   co = __builtin_fmaf(0.5f, r, c);
 }
 // the same on four coordinates; d: one agent's weight (agent-major) or four agents' (parameter-major)
@@ -509,15 +548,21 @@ struct ExtraArgs {
   int32_t objective; float lr;
 };
 
-// X, Y: the mix's own pair (the mix's preamble checks them; here only against corr)
-inline int check_extra(const char* nm, const ExtraArgs& e, const float* X, const float* Y, int64_t P, bool* evec) {
-  if (!e.T) return fail(DOL_EINVAL, "%s: null target", nm);
+// X, Y: the mix's own pair (the mix's preamble checks them; here only against
+// corr).  fed: the gradient-fed round, whose T is the gradient matrix G (its
+// name in the messages; no objective; G must not be the output Y either).
+inline int check_extra(const char* nm, const ExtraArgs& e, const float* X, const float* Y, int64_t P, bool* evec,
+                       bool fed = false) {
+  if (!e.T) return fail(DOL_EINVAL, "%s: null %s", nm, fed ? "G" : "target");
   if (!e.C) return fail(DOL_EINVAL, "%s: null corr", nm);
-  if (e.objective != 0 && e.objective != 1) return fail(DOL_EINVAL, "%s: objective must be 0 (least squares) or 1 (logistic)", nm);
-  if (e.ldt < P) return fail(DOL_EINVAL, "%s: ldt < P", nm);
+  if (!fed && e.objective != 0 && e.objective != 1)
+    return fail(DOL_EINVAL, "%s: objective must be 0 (least squares) or 1 (logistic)", nm);
+  if (e.ldt < P) return fail(DOL_EINVAL, "%s: %s < P", nm, fed ? "ldg" : "ldt");
   if (e.ldc < P) return fail(DOL_EINVAL, "%s: ldc < P", nm);
   if (e.C == X || e.C == Y || e.C == e.T)
-    return fail(DOL_EINVAL, "%s: corr aliases X, Y or target (the correction is updated in place)", nm);
+    return fail(DOL_EINVAL, "%s: corr aliases X, Y or %s (the correction is updated in place)", nm,
+                fed ? "G" : "target");
+  if (fed && e.T == Y) return fail(DOL_EINVAL, "%s: G aliases Y (the gradient rows are read while Y is written)", nm);
   *evec = row_vec_ok(e.T, e.ldt) && row_vec_ok(e.C, e.ldc);
   return DOL_OK;
 }
@@ -540,6 +585,24 @@ int with_extra_epi(const char* nm, const ExtraArgs& e, const float* X, int64_t l
     return f(ExtraEpi<decltype(obj)::value, decltype(self)::value, CENTRE>{e.T, e.ldt, e.C, e.ldc, X, ldx, e.self_w, -e.lr, nt},
              evec);
   }, Ints<0, 1>{e.objective}, Bool{e.self_w != nullptr});
+}
+
+// The same for the gradient-fed round: e.T is the gradient matrix G, e.objective
+// is not read, and the epilogue is ExtraEpi<kObjGradRow, ...>, which no other
+// path instantiates.
+template <bool CENTRE, class F>
+int with_extra_grad_epi(const char* nm, const ExtraArgs& e, const float* X, int64_t ldx, const float* Y, bool empty,
+                        int64_t P, F&& f) {
+  bool evec = false;
+  if (!empty) {
+    const int rc = check_extra(nm, e, X, Y, P, &evec, true);
+    if (rc) return rc;
+  }
+  const int nt = epi_nt_policy(P);
+  return dispatch([&](auto self) {
+    return f(ExtraEpi<kObjGradRow, decltype(self)::value, CENTRE>{e.T, e.ldt, e.C, e.ldc, X, ldx, e.self_w, -e.lr, nt},
+             evec);
+  }, Bool{e.self_w != nullptr});
 }
 
 }  // namespace

@@ -99,8 +99,12 @@ SIGNATURES = {
                        _i32, _f32, _ptr],
     "dol_gt_push_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
                             _i64, _i32, _f32, _ptr, _ptr, _ptr],
+    "dol_gt_grad_csr_f32": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                            _i64, _ptr, _i64, _f32, _ptr],
     "dol_extra_csr_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i32, _f32,
                           _ptr],
+    "dol_extra_grad_csr_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _f32,
+                               _ptr],
     "dol_extra_ring_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64,
                            _i32, _f32, _ptr],
     "dol_extra_ring_edges_f32": [_ptr, _i64, _ptr, _i64, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr,

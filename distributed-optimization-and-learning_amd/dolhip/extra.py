@@ -5,7 +5,11 @@ or the blocks of a sharded ring through its halo form) and on a ring block's
 two boundary rows (dol_extra_ring_edges_f32), and on the parameter-major bank
 with any sparse W up to ops.PM_DGD_MAX_AGENTS agents (dol_extra_csr_pm_f32).
 ops re-exports the calls as ops.extra_csr / ops.extra_ring /
-ops.extra_ring_edges / ops.extra_csr_pm.
+ops.extra_ring_edges / ops.extra_csr_pm.  extra_grad_csr
+(dol_extra_grad_csr_f32, ops.extra_grad_csr) is extra_csr's round with the
+gradient fed as a row matrix, for agents whose gradients are not a separable
+loss of a target row (the per-agent MLPs of config 5); its rules are pinned by
+tests/test_grad_rounds_host.py.
 
 With W~ = (I + W) / 2 the paper's recursion
   x(k+2) = (I + W) x(k+1) - W~ x(k) - lr [grad f(x(k+1)) - grad f(x(k))],   x(1) = W x(0) - lr grad f(x(0))
@@ -89,6 +93,39 @@ def extra_csr(X: torch.Tensor, Y: torch.Tensor, rowptr: torch.Tensor, col: torch
     _native.call("dol_extra_csr_f32", X.data_ptr(), ldx, Y.data_ptr(), ldy, n, P, rowptr.data_ptr(),
                  _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val), _ops._ptr(self_weight), target.data_ptr(),
                  ldt, corr.data_ptr(), ldc, obj, float(lr), _ops._stream(X))
+    return Y
+
+
+def extra_grad_csr(X: torch.Tensor, Y: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor,
+                   G: torch.Tensor, corr: torch.Tensor, self_weight: Optional[torch.Tensor] = None, lr: float = 0.01,
+                   P: Optional[int] = None) -> torch.Tensor:
+    """extra_csr's round with the gradient FED as the row matrix G
+    (dol_extra_grad_csr_f32), read where extra_csr reads the target: for agents
+    whose gradients something else computes (BatchedMLP.forward_backward writes
+    them into the bank's grad rows).  Per coordinate
+      ax, the self term and r as extra_csr
+      x' = fl(fma(-lr, g_i, ax) - c_i);  c' = fma(0.5, r, c_i)
+    the bits of extra_csr when G holds g(x_i, t_i).  corr is zero before the
+    first round and updated in place.  The rules of this op are extra_csr's
+    without an objective, with G in target's place (Y is not X; corr is none of
+    X, Y, G; a self-weight vector of n floats; a square W), and: G is not Y.
+    Returns Y."""
+    for nm, t in (("G", G), ("corr", corr)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"extra_grad_csr: {nm}: expected a torch.Tensor")
+    for nm, t in (("X", X), ("Y", Y), ("G", G)):
+        if corr is t or (isinstance(t, torch.Tensor) and corr.data_ptr() == t.data_ptr()):
+            raise ValueError(f"extra_grad_csr: corr and {nm} alias: the correction is updated in place")
+    if G is Y or (isinstance(Y, torch.Tensor) and G.data_ptr() == Y.data_ptr()):
+        raise ValueError("extra_grad_csr: G and Y alias: the gradient rows are read while Y is written")
+    P, n, ldx, ldy = _ops._csr_args(X, Y, rowptr, col, val, P, same_length=False)
+    _, ldc, ldg = _leading_dims((("X", X), ("corr", corr)), ("G", G), P, n)
+    if self_weight is not None:
+        _ops._check_array("self_weight", self_weight, torch.float32, n, X.device)
+    _check_square(rowptr, col, n)
+    _native.call("dol_extra_grad_csr_f32", X.data_ptr(), ldx, Y.data_ptr(), ldy, n, P, rowptr.data_ptr(),
+                 _ops._ptr_unless_empty(col), _ops._ptr_unless_empty(val), _ops._ptr(self_weight), G.data_ptr(), ldg,
+                 corr.data_ptr(), ldc, float(lr), _ops._stream(X))
     return Y
 
 

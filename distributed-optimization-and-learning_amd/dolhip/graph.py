@@ -640,6 +640,38 @@ class MixingPlan:
         return ops.gt_push_csr(U, S, UO, SO, self.rowptr, self.col, self.val, target, v, v_out,
                                self_weight=self_weight, objective=objective, lr=lr, P=P)
 
+    def _fed_round_plan(self, what: str) -> None:
+        """The plans the gradient-fed rounds run on: CSR only."""
+        if self.kind == "ring":
+            raise NotImplementedError(f"the {what} round runs on a CSR plan; build this one with allow_ring=False")
+        if self.kind == "dense":
+            raise NotImplementedError(f"{what} rounds are fused into the sparse mixes; use a CSR plan")
+
+    def apply_gt_grad(self, X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, G: torch.Tensor,
+                      Gprev: torch.Tensor, self_weight: Optional[torch.Tensor] = None, lr: float = 0.01,
+                      P: Optional[int] = None):
+        """One gradient-tracking round with the gradient fed as the row
+        matrices G / Gprev (ops.gt_grad_csr) and W = this plan's W +
+        diag(self_weight); CSR plans only (the ring kernel has no fed form:
+        build the plan with allow_ring=False).  A CSR plan that carries a slab
+        pack still runs ops.gt_grad_csr, as apply_gt does.  Returns (XO, SO)."""
+        from . import ops
+        self._check_x(X)
+        self._fed_round_plan("gradient-fed gradient-tracking")
+        return ops.gt_grad_csr(X, S, XO, SO, self.rowptr, self.col, self.val, G, Gprev, self_weight=self_weight, lr=lr,
+                               P=P)
+
+    def apply_extra_grad(self, X: torch.Tensor, Y: torch.Tensor, G: torch.Tensor, corr: torch.Tensor,
+                         self_weight: Optional[torch.Tensor] = None, lr: float = 0.01,
+                         P: Optional[int] = None) -> torch.Tensor:
+        """One EXTRA round with the gradient fed as the row matrix G
+        (ops.extra_grad_csr) and W = this plan's W + diag(self_weight); CSR
+        plans only, as apply_gt_grad.  corr is updated in place.  Returns Y."""
+        from . import ops
+        self._check_x(X)
+        self._fed_round_plan("gradient-fed EXTRA")
+        return ops.extra_grad_csr(X, Y, self.rowptr, self.col, self.val, G, corr, self_weight=self_weight, lr=lr, P=P)
+
 
 def plans_for(graphs: Sequence[Graph], device, allow_ring: bool = True) -> List[MixingPlan]:
     return [MixingPlan.from_graph(g, device, allow_ring) for g in graphs]

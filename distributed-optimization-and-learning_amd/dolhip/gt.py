@@ -29,6 +29,11 @@ gt_push_csr (dol_gt_push_csr_f32, ops.gt_push_csr) is the push-sum form of
 gt_csr's round for weights that are column-stochastic only (ADD-OPT /
 Push-DIGing): one more scalar per agent and the gradients taken at U / v; its
 arithmetic and rules are in its docstring, pinned by tests/test_gt_push_host.py.
+
+gt_grad_csr (dol_gt_grad_csr_f32, ops.gt_grad_csr) is gt_csr's round with the
+gradient fed as a row matrix, for agents whose gradients are not a separable
+loss of a target row (the per-agent MLPs of config 5); its arithmetic and rules
+are in its docstring, pinned by tests/test_grad_rounds_host.py.
 """
 from __future__ import annotations
 
@@ -248,6 +253,48 @@ def gt_push_csr(U: torch.Tensor, S: torch.Tensor, UO: torch.Tensor, SO: torch.Te
                            self_weight, objective, lr, P, vectors=(("v", v), ("v_out", v_out)), then=distinct_v)
     _native.call("dol_gt_push_csr_f32", *call, v.data_ptr(), v_out.data_ptr(), _ops._stream(U))
     return UO, SO, v_out
+
+
+def gt_grad_csr(X: torch.Tensor, S: torch.Tensor, XO: torch.Tensor, SO: torch.Tensor, rowptr: torch.Tensor,
+                col: torch.Tensor, val: torch.Tensor, G: torch.Tensor, Gprev: torch.Tensor,
+                self_weight: Optional[torch.Tensor] = None, lr: float = 0.01,
+                P: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One gradient-tracking round on the agent-major bank with the gradient
+    FED as a row matrix (dol_gt_grad_csr_f32), for agents whose gradients
+    something else computes (BatchedMLP.forward_backward writes them into the
+    bank's grad rows): X the parameters, S the trackers, G this round's
+    gradients, Gprev the previous round's, [>= n, >= P] like gt_csr's X; XO / SO
+    receive x' / s'.  W = W_off + diag(self_weight) as gt_csr's.  DIGing with
+    the tracker update at the front of the round, per coordinate, all fp32, one
+    rounding each
+      ax = mix of x, as = mix of s                     (mix_csr's sums)
+      ax = fl(ax + fl(d_i x_i)), as = fl(as + fl(d_i s_i))     with self_weight
+      s' = fl(fl(as + g_i) - gprev_i);  x' = fma(-lr, s', ax)
+    x' takes the agent's own new tracker, so the round is one pass.  Start from
+    S = 0 and Gprev = 0 (the first round then gives s = G: no separate
+    initialisation) and swap G and Gprev after every call.  The rules of this
+    op are gt_csr's without an objective (the four state matrices distinct; a
+    self-weight vector of n floats; a square W), with G and Gprev in target's
+    place, and: neither G nor Gprev is XO or SO.  Returns (XO, SO)."""
+    name = "gt_grad_csr"
+    n = rowptr.shape[0] - 1
+    state = (("X", X), ("S", S), ("XO", XO), ("SO", SO))
+    _distinct_state(name, state)
+    for ng, g in (("G", G), ("Gprev", Gprev)):
+        for no, o in state[2:]:
+            if g is o or (isinstance(g, torch.Tensor) and g.data_ptr() == o.data_ptr()):
+                raise ValueError(f"{name}: {ng} and {no} alias: the gradient rows are read while the outputs are written")
+    if self_weight is not None:
+        _ops._check_array("self_weight", self_weight, torch.float32, n, X.device)
+    P = X.shape[1] if P is None else P
+    lds = _leading_dims(state + (("G", G),), ("Gprev", Gprev), P, n)
+    _ops._check_csr(rowptr, col, val, X.device, same_length=False)
+    _check_square(rowptr, col, n)
+    rows = tuple(a for (_, t), ld in zip(state, lds) for a in (t.data_ptr(), ld))
+    _native.call("dol_gt_grad_csr_f32", *rows, n, P, rowptr.data_ptr(), _ops._ptr_unless_empty(col),
+                 _ops._ptr_unless_empty(val), _ops._ptr(self_weight), G.data_ptr(), lds[4], Gprev.data_ptr(), lds[5],
+                 float(lr), _ops._stream(X))
+    return XO, SO
 
 
 def separable_grad(X: torch.Tensor, T: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -1085,14 +1085,15 @@ from .pm_steps import dgd_csr_pm_steps, mix_csr_pm_steps, pm_steps_passes  # noq
 # on the agent-major bank with any sparse W (gt.py, which builds on the
 # validators above and on pm_steps' square-W check): gt_csr_pm, gt_ring,
 # gt_ring_edges (a sharded ring block's two boundary rows), gt_csr,
-# separable_grad; and gt_csr's push-sum form for column-stochastic weights,
-# gt_push_csr.
+# separable_grad; gt_csr's push-sum form for column-stochastic weights,
+# gt_push_csr; and its form with the gradient fed as a row matrix, gt_grad_csr.
 # ---------------------------------------------------------------------------
-from .gt import gt_csr, gt_csr_pm, gt_push_csr, gt_ring, gt_ring_edges, separable_grad  # noqa: E402,F401
+from .gt import gt_csr, gt_csr_pm, gt_grad_csr, gt_push_csr, gt_ring, gt_ring_edges, separable_grad  # noqa: E402,F401
 
 # ---------------------------------------------------------------------------
 # EXTRA, the exact round that mixes the parameters only, on the agent-major
 # bank and ring and on the parameter-major bank (extra.py, on the validators
-# above and gt.py's): extra_csr, extra_ring, extra_ring_edges, extra_csr_pm.
+# above and gt.py's): extra_csr, extra_ring, extra_ring_edges, extra_csr_pm;
+# and extra_csr with the gradient fed as a row matrix, extra_grad_csr.
 # ---------------------------------------------------------------------------
-from .extra import extra_csr, extra_csr_pm, extra_ring, extra_ring_edges  # noqa: E402,F401
+from .extra import extra_csr, extra_csr_pm, extra_grad_csr, extra_ring, extra_ring_edges  # noqa: E402,F401

@@ -497,6 +497,40 @@ int dol_gt_push_csr_f32(const float* U, int64_t ldu, const float* S, int64_t lds
                         int32_t objective, float lr, const float* v, float* v_out, hipStream_t s);
 
 /*
+ * One gradient-tracking round on the agent-major bank with any sparse W in one
+ * pass, with the gradient FED as a row matrix instead of computed in the kernel:
+ * for agents whose gradients something else computes (the per-agent MLPs of
+ * BASELINE config 5, whose dol_mlp_step_f32 with update == 0 writes them into
+ * the bank's grad rows; autograd into bank rows).  Not in the reference: it
+ * replaces the consensus + local step round of DIST/simulators.py:147-162 (a
+ * biased fixed point under a constant step size); the mix inside is its
+ * consensus (DIST/clients.py:61-69) in dol_mix_csr_f32's rounding.  DIGing with
+ * the tracker update at the front of the round: s(k) = W s(k-1) + G(k) -
+ * G(k-1), then x(k+1) = W x(k) - lr s(k).  X, S, XO, SO, G (this round's
+ * gradients) and Gprev (the previous round's) are row matrices of n rows in
+ * dol_gt_csr_f32's layout; W = W_off + diag(self_w) as there.  For every row i
+ * and column c, all fp32, each operation rounded once:
+ *   ax = sum_e val[e] * x[col[e]]      (+0 start, ascending e, product and sum rounded separately)
+ *   as = the same over s
+ *   self_w != NULL:  ax = fl(ax + fl(self_w[i]*x_i));  as = fl(as + fl(self_w[i]*s_i))
+ *   s' = fl(fl(as + g_i) - gprev_i)
+ *   x' = fma(-lr, s', ax)
+ * x' takes the agent's own new tracker, so the round is one pass.  Start from S
+ * = 0 and Gprev = 0: the first round gives s(0) = G(0), so there is no separate
+ * initialisation; after the call the caller swaps G and Gprev.  Argument rules
+ * as dol_gt_csr_f32 with G and Gprev in target's place (no objective), and:
+ * neither G nor Gprev is XO or SO.  16-B columns where the six matrices are 16-B
+ * aligned with ld % 4 == 0, else scalar.  The round gathers X and S, reads G and
+ * Gprev once and writes XO and SO once: six streams to dol_gt_csr_f32's five;
+ * without self weights the centre rows of X and S are not read.  Stream-ordered;
+ * allocates nothing; does not synchronise.
+ */
+int dol_gt_grad_csr_f32(const float* X, int64_t ldx, const float* S, int64_t lds, float* XO, int64_t ldxo, float* SO,
+                        int64_t ldso, int32_t n, int64_t P, const int32_t* rowptr, const int32_t* col,
+                        const float* val, const float* self_w /* nullable */, const float* G, int64_t ldg,
+                        const float* Gprev, int64_t ldgp, float lr, hipStream_t s);
+
+/*
  * One EXTRA round (Shi, Ling, Wu, Yin, "EXTRA: an exact first-order algorithm
  * for decentralized consensus optimization", SIAM J. Optim. 25(2), 2015) of
  * BASELINE config 3 on the agent-major bank with any sparse W in one pass.  With
@@ -528,6 +562,22 @@ int dol_gt_push_csr_f32(const float* U, int64_t ldu, const float* S, int64_t lds
 int dol_extra_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n, int64_t P, const int32_t* rowptr,
                       const int32_t* col, const float* val, const float* self_w /* nullable */, const float* target,
                       int64_t ldt, float* corr, int64_t ldc, int32_t objective, float lr, hipStream_t s);
+/*
+ * dol_extra_csr_f32's round (Shi, Ling, Wu, Yin 2015; not in the reference, in
+ * place of DIST/simulators.py:147-162 with the consensus of DIST/clients.py:61-69)
+ * with the gradient FED as the row matrix G, read where that entry reads the
+ * target: for agents whose gradients something else computes (see
+ * dol_gt_grad_csr_f32).  For every row i and column c:
+ *   ax, the self term and r as dol_extra_csr_f32
+ *   x' = fl(fma(-lr, g_i, ax) - c_i);   c' = fma(0.5, r, c_i)   written over c_i
+ * the bits of dol_extra_csr_f32 when G holds g(x_i, t_i).  Start with corr = 0.
+ * The same five streams.  Argument rules as dol_extra_csr_f32 with G in target's
+ * place (no objective), and: G is not Y.
+ */
+int dol_extra_grad_csr_f32(const float* X, int64_t ldx, float* Y, int64_t ldy, int32_t n, int64_t P,
+                           const int32_t* rowptr, const int32_t* col, const float* val,
+                           const float* self_w /* nullable */, const float* G, int64_t ldg, float* corr, int64_t ldc,
+                           float lr, hipStream_t s);
 /*
  * dol_extra_csr_f32's round (Shi, Ling, Wu, Yin 2015; not in the reference, in
  * place of DIST/simulators.py:147-162 with the consensus of DIST/clients.py:61-69)
